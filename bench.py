@@ -9,6 +9,13 @@ contiguous shards, one per GPU, so total work per step is fixed (strong
 scaling).  Inputs (the planet, the lists) are resident in HBM before timing.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload r64n7|r128n6|gcp]
+                  [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times the K steps and prints the line.
+--dump-outputs DIR also writes the last timed step's result as DIR/<name>.npy
+(dump_outputs).  --full adds everything beyond the headline figure: the check
+of the result against its fixture under tests/golden/, the CPU baseline
+(--no-cpu-baseline leaves it out) and the oracle's re-derivation of the
+reported records.
   N>1: python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...
        or python bench.py --gpus N, which starts the N ranks itself
        (fantoch_amd/launch.py; the launching process never touches the GPU).
@@ -232,8 +239,8 @@ def main_gcp(args):
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     kern = sum(sw.timing()[0] for sw in sweeps) / max(args.steps, 1)
-    fx = json.load(open(os.path.join(ROOT, "tests", "golden", "topk.json")))
-    for n, r in zip(GCP_NS, res):
+    fx = json.load(open(os.path.join(ROOT, "tests", "golden", "topk.json"))) if args.full else None
+    for n, r in (zip(GCP_NS, res) if fx else ()):  # (--full: each n against its oracle fixture)
         c = fx["cases"][f"gcp_n{n}"]
         K = fx["K"]
         if (r.valid, str(r.digest)) != (c["valid"], c["digest"]) or \
@@ -253,10 +260,14 @@ def main_gcp(args):
                      "frac": achieved / VALU_PEAK_TOPS, "traffic": None, "work_per_config": "SURVEY W(n, 20)",
                      "kernel_ms_per_step": kern,
                      "note": "six sweeps of 1,140..167,960 configs: launch- and merge-bound, not a roofline case"},
-        "result_check": {"fixture": "every n equal to tests/golden/topk.json (oracle, all ranks)",
+        "result_check": {"fixture": "every n equal to tests/golden/topk.json (oracle, all ranks)" if fx else
+                                    "not checked (a plain run; --full compares every n with its fixture)",
                          "valid": [r.valid for r in res]},
     }
-    if not args.no_cpu_baseline:
+    if args.dump_outputs:
+        for sw, r in zip(sweeps, res):
+            dump_outputs(args.dump_outputs, sw.objectives, sw.K, r, prefix=f"n{sw.n}_")
+    if args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline_gcp(planet)
     print(json.dumps(out), flush=True)
 
@@ -375,16 +386,67 @@ def profile_figures(pmc, traffic, build, shard, kavg_ms):
     return valu, tb, stale
 
 
+def key_values(kind, keys):
+    """Top-K record keys (uint64, include/bote_hip.h bote_topk_record) as the
+    float64 figures they order by: SCORE: the score (key = ~orderable(score));
+    MEAN: the histogram's integer sum (far below 2^53); COV: fl64(V / S1^2)
+    (key = its IEEE bits; all-ones, a NaN, where the COV is NaN)."""
+    import numpy as np
+
+    from fantoch_amd import _lib
+
+    k = np.ascontiguousarray(keys, dtype=np.uint64)
+    if kind == _lib.OBJ_SCORE:
+        o = ~k
+        sign = np.uint64(0x8000000000000000)
+        return np.where(o >> np.uint64(63), o ^ sign, ~o).view(np.float64)
+    if kind == _lib.OBJ_COV:
+        return k.view(np.float64)
+    return k.astype(np.float64)
+
+
+def dump_outputs(out_dir, objectives, K, res, prefix=""):
+    """--dump-outputs: the SweepResult the timed path returned in its last
+    step, as float64 .npy files under out_dir (a few KB in all):
+      <prefix>tops_value  (objectives, K) each record's key as key_values() gives it
+      <prefix>tops_rank   (objectives, K) each record's colex rank (< 2^53)
+      <prefix>tops_count  (objectives,)   records in each list; the rest of a row is -1
+      <prefix>valid       (1,)            valid configs (< 2^53)
+      <prefix>digest      (2,)            the 64-bit digest as its high and low 32 bits"""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    no = len(objectives)
+    value = np.full((no, K), -1.0)
+    rank = np.full((no, K), -1.0)
+    count = np.zeros(no)
+    for o, ((kind, _), lst) in enumerate(zip(objectives, res.tops)):
+        count[o] = len(lst)
+        if lst:
+            recs = np.array(lst, dtype=np.uint64).reshape(-1, 2)
+            value[o, :len(lst)] = key_values(kind, recs[:, 0])
+            rank[o, :len(lst)] = recs[:, 1].astype(np.float64)
+    for name, a in (("tops_value", value), ("tops_rank", rank), ("tops_count", count),
+                    ("valid", np.array([float(res.valid)])),
+                    ("digest", np.array([float(res.digest >> 32), float(res.digest & 0xFFFFFFFF)]))):
+        np.save(os.path.join(out_dir, f"{prefix}{name}.npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--workload", default="r64n7", choices=list(workloads()))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's result as DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="beyond the headline figure: check the result against its fixture, run the CPU baseline "
+                         "and have the oracle re-derive the reported records")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--skip-fixture-check", action="store_true",
-                    help="diagnostics (A/B timing while a fixture is being re-pinned): no result check; the line "
-                         "says so and is not a bench line to quote")
+                    help="with --full, diagnostics (A/B timing while a fixture is being re-pinned): no result "
+                         "check; the line says so and is not a bench line to quote")
     args = ap.parse_args()
     # a timing-diagnostics environment must not produce a bench line
     for var in ("BOTE_ABLATE", "BOTE_SWEEP_KERNEL", "BOTE_FORCE_GENERIC", "BOTE_NO_DEF_OBJ", "BOTE_CHUNKS_PER_WAVE"):
@@ -497,8 +559,10 @@ def main():
 
     # the result must equal the oracle-pinned full sweep, or config 5's
     # regression pin (every rank holds the merged result)
-    fx, label = (None, None) if args.skip_fixture_check else load_fixture(args.workload)
+    fx, label = load_fixture(args.workload) if args.full and not args.skip_fixture_check else (None, None)
     check = "SKIPPED (--skip-fixture-check: diagnostics, not a bench line)" if args.skip_fixture_check else "no fixture"
+    if not args.full:
+        check = "not checked (a plain run; --full compares the result with its fixture)"
     if fx is not None:
         assert (fx["rank_begin"], fx["rank_end"]) == (0, total)
         want = (int(fx["valid"]), int(fx["digest"]), [[(int(k), int(r)) for k, r in t] for t in fx["tops"]])
@@ -575,7 +639,9 @@ def main():
             out["rehearsal"] = f"{world} ranks on {census['distinct_devices']} GPU(s) over gloo: not a bench line"
         if os.environ.get("BOTE_LIB_PATH"):
             out["config"]["lib_path"] = os.environ["BOTE_LIB_PATH"]  # an A/B build, not the product library
-        if not args.no_cpu_baseline:  # (after the timed region; at N > 1 on rank 0 only)
+        if args.dump_outputs:  # (every rank holds the merged result: rank 0 writes it)
+            dump_outputs(args.dump_outputs, objectives, sweep.K, res)
+        if args.full and not args.no_cpu_baseline:  # (after the timed region; at N > 1 on rank 0 only)
             out["cpu_baseline"] = cpu_baseline(planet, n, wl["keys"], objectives)
             if fx is not None and "pin" in check:
                 # a regression pin is not an oracle sweep: the oracle re-derives what it can, every reported record

@@ -8,7 +8,7 @@
 # Steps (outputs under gpurun_out/$TAG/):
 #   smoke    __graft_entry__.py (smoke on cuda:0)
 #   tests    pytest -m gpu over TEST_FILES (default tests/; PYTEST_EXPR: a -k expression)
-#   bench    bench.py with the CPU baseline, for each workload in BWLS (default WLS)
+#   bench    bench.py --full (fixture check, CPU baseline), for each workload in BWLS (default WLS)
 #   ab       A/B timing of library variants: VARIANTS="default lib_x ..." (lib_x:
 #            fantoch_amd/lib_x/libbote_hip.so, scripts/build_variant.sh), REPS
 #            rounds interleaved, for each workload in WLS; AB_SKIP=1 passes
@@ -53,7 +53,7 @@ step_tests() {
 
 step_bench() {
   for wl in ${BWLS:-$WLS}; do
-    timeout -k 10 400 python -u bench.py --workload "$wl" --steps "${BSTEPS:-20}" --warmup 2 ${BENCH_ARGS:-} \
+    timeout -k 10 400 python -u bench.py --full --workload "$wl" --steps "${BSTEPS:-20}" --warmup 2 ${BENCH_ARGS:-} \
       > "$O/bench_$wl.log" 2>&1 || fail "bench $wl" $? "$O/bench_$wl.log"
     echo "bench $wl: $(grep -o '"ms_per_step": [0-9.]*\|"kernel_ms_avg": [0-9.]*\|"fixture": "[^"]*' "$O/bench_$wl.log" | tr '\n' ' ')"
   done
@@ -66,7 +66,7 @@ step_ab() {
     for wl in $WLS; do
       for V in ${VARIANTS:-default}; do
         if [ "$V" = default ]; then unset BOTE_LIB_PATH; else export BOTE_LIB_PATH=fantoch_amd/$V/libbote_hip.so; fi
-        timeout -k 10 300 python -u bench.py --workload "$wl" --steps "${ABSTEPS:-10}" --warmup 2 --no-cpu-baseline $skip \
+        timeout -k 10 300 python -u bench.py --full --workload "$wl" --steps "${ABSTEPS:-10}" --warmup 2 --no-cpu-baseline $skip \
           > "$O/ab_${wl}_${V}_$r.log" 2>&1 || fail "ab $wl $V" $? "$O/ab_${wl}_${V}_$r.log"
         echo "ab $wl $V #$r: $(grep -o '"kernel_ms_avg": [0-9.]*\|"ms_per_step": [0-9.]*\|"valid": [0-9]*\|"digest": [0-9]*' "$O/ab_${wl}_${V}_$r.log" | tr '\n' ' ')"
       done

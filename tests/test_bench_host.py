@@ -69,6 +69,32 @@ def test_profile_figures_only_for_the_profiled_build():
     assert valu["util"] is None and tb is None and len(stale) == 1
 
 
+def test_dump_outputs_round_trips_a_result(tmp_path):
+    """--dump-outputs: every record's key comes back as the figure it orders by
+    (include/bote_hip.h bote_topk_record), short lists are padded with -1, and
+    the 64-bit digest is exact as two 32-bit halves."""
+    import numpy as np
+
+    from fantoch_amd import _lib
+    from fantoch_amd.bote import SweepResult, _orderable
+
+    scores = np.array([250.5, 0.0, -3.25])
+    covs = np.array([0.125, 0.5])
+    tops = [[(int(k), r) for k, r in zip(~_orderable(scores), (7, 8, 9))],
+            [(1234, 5), (1234, 6), (99999, 1)],
+            [(int(k), r) for k, r in zip(covs.view(np.uint64), (621216191, 3))]]
+    objs = [(_lib.OBJ_SCORE, 0), (_lib.OBJ_MEAN, _lib.SLOT_AF1), (_lib.OBJ_COV, _lib.SLOT_AF1)]
+    digest = 0xFEDCBA9876543210
+    bench.dump_outputs(str(tmp_path / "d"), objs, 4, SweepResult(tops, 32380967, digest), prefix="p_")
+    got = {n: np.load(tmp_path / "d" / f"p_{n}.npy") for n in ("tops_value", "tops_rank", "tops_count", "valid",
+                                                              "digest")}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert got["tops_count"].tolist() == [3, 3, 2] and got["valid"].tolist() == [32380967]
+    assert got["tops_value"].tolist() == [[250.5, 0.0, -3.25, -1], [1234, 1234, 99999, -1], [0.125, 0.5, -1, -1]]
+    assert got["tops_rank"].tolist() == [[7, 8, 9, -1], [5, 6, 1, -1], [621216191, 3, -1, -1]]
+    assert (int(got["digest"][0]) << 32) | int(got["digest"][1]) == digest
+
+
 def test_lib_build_is_the_loaded_library():
     from fantoch_amd import _lib
 
