@@ -662,23 +662,15 @@ int bote_sweep_create_ex(const bote_planet* p, const uint32_t* servers, uint32_t
   return bote_sweep_create_keys(p, servers, ns, clients, nc, n, objs, n_obj, K, rp, digest, kernel, 0, out);
 }
 
-// slot s exists for config size n (f = 2 keys need max_f >= 2); slots >= 10
-// only with the extended key set
-static bool slot_exists_n(uint32_t n, uint32_t slot, uint32_t keys) {
-  const bool f2 = bote_max_f(n) >= 2;
-  if (slot < 10) {
-    const uint32_t b = slot % 5;
-    return !((b == BOTE_SLOT_AF2 || b == BOTE_SLOT_FF2) && !f2);
-  }
-  if (!keys || slot >= BOTE_NSLOTS_X) return false;
-  if (slot < 18) return (slot - 10) % 2 == 0 || f2;
-  return slot == 18 || f2;
-}
+// bote_sweep_create_keys in steps.  Each returns a BOTE_E_* code (the entry
+// point destroys the half-built sweep on a failure); the pure arithmetic
+// behind them is bote_host.cpp's (fast_limits, score_bands, ...).
 
-int bote_sweep_create_keys(const bote_planet* p, const uint32_t* servers, uint32_t ns, const uint32_t* clients,
-                           uint32_t nc, uint32_t n, const bote_objective* objs, uint32_t n_obj, uint32_t K,
-                           const bote_ranking_params* rp, int digest, int kernel, uint32_t keys, bote_sweep** out) {
-  DevGuard dev_guard;  // the caller's current device is restored on return
+// Step 1, before anything is allocated: the argument checks.
+static int sweep_check_args(const bote_planet* p, const uint32_t* servers, uint32_t ns, const uint32_t* clients,
+                            uint32_t nc, uint32_t n, const bote_objective* objs, uint32_t n_obj, uint32_t K,
+                            const bote_ranking_params* rp, int kernel, uint32_t keys, bote_sweep** out,
+                            bool& has_score) {
   int rc;
   if (!out) return fail(BOTE_E_ARG, "out is null");
   if (keys > BOTE_KEYS_TEMPO_ALL_LEADERS) return fail(BOTE_E_ARG, "unknown key set");
@@ -687,7 +679,7 @@ int bote_sweep_create_keys(const bote_planet* p, const uint32_t* servers, uint32
   if (n_obj > BOTE_MAX_OBJECTIVES) return fail(BOTE_E_RANGE, "more than 8 objectives");
   if (n_obj && !objs) return fail(BOTE_E_ARG, "objectives null");
   if (K == 0 || K > BOTE_MAX_K) return fail(BOTE_E_RANGE, "K must be in [1, 128]");
-  bool has_score = false;
+  has_score = false;
   for (uint32_t o = 0; o < n_obj; ++o) {
     if (objs[o].kind > BOTE_OBJ_COV) return fail(BOTE_E_ARG, "unknown objective kind");
     if (objs[o].kind == BOTE_OBJ_SCORE) {
@@ -699,28 +691,26 @@ int bote_sweep_create_keys(const bote_planet* p, const uint32_t* servers, uint32
   }
   if (has_score && !rp) return fail(BOTE_E_ARG, "SCORE objective needs ranking params");
   if (rp && rp->ft_metric != BOTE_FT_F1 && rp->ft_metric != BOTE_FT_F1F2) return fail(BOTE_E_ARG, "bad ft_metric");
-  HIP_TRY(hipSetDevice(p->device));
-  auto* s = new bote_sweep();
-  auto cleanup = [&](int code) {
-    bote_sweep_destroy(s);
-    return code;
-  };
-  s->p = p;
-  s->n = n;
-  s->ns = ns;
-  s->nc = nc;
-  s->n_obj = n_obj;
-  s->K = K;
+  return BOTE_OK;
+}
+
+// Step 2: the server, client and binomial lists on the device, the generic
+// kernel's arguments (s->args) and its launch geometry.
+static int sweep_upload_lists(bote_sweep* s, const uint32_t* servers, const uint32_t* clients,
+                              const bote_objective* objs, const bote_ranking_params* rp, bool has_score, int digest,
+                              uint32_t keys) {
+  const bote_planet* p = s->p;
+  const uint32_t n = s->n, ns = s->ns, nc = s->nc, n_obj = s->n_obj;
   EvalArgs& a = s->args;
   a = EvalArgs{};
   auto t = binom_table(ns, n);
   if (s->srv.alloc(ns * 4) != hipSuccess || s->cli.alloc(nc * 4) != hipSuccess ||
       s->binom.alloc(t.size() * 8) != hipSuccess || s->counters.alloc(16) != hipSuccess)
-    return cleanup(fail(BOTE_E_NOMEM, "hipMalloc sweep lists"));
+    return fail(BOTE_E_NOMEM, "hipMalloc sweep lists");
   if (hipMemcpy(s->srv.p, servers, ns * 4, hipMemcpyHostToDevice) != hipSuccess ||
       (nc && hipMemcpy(s->cli.p, clients, nc * 4, hipMemcpyHostToDevice) != hipSuccess) ||
       hipMemcpy(s->binom.p, t.data(), t.size() * 8, hipMemcpyHostToDevice) != hipSuccess)
-    return cleanup(fail(BOTE_E_DEVICE, "upload sweep lists"));
+    return fail(BOTE_E_DEVICE, "upload sweep lists");
   a.mat = p->d_mat;
   a.R = p->R;
   a.srv = s->srv.as<uint32_t>();
@@ -735,7 +725,7 @@ int bote_sweep_create_keys(const bote_planet* p, const uint32_t* servers, uint32
     a.obj_kind[o] = objs[o].kind;
     a.obj_slot[o] = objs[o].slot;
   }
-  a.K = K;
+  a.K = s->K;
   a.want_digest = digest ? 1 : 0;
   a.keys = keys;
   a.out_counters = s->counters.as<unsigned long long>();
@@ -744,268 +734,287 @@ int bote_sweep_create_keys(const bote_planet* p, const uint32_t* servers, uint32
   a.out_top = (Rec*)1;  // sizing with top-K structures
   s->shm = bote::eval_smem_bytes(a, n, s->bd, true);
   a.out_top = nullptr;
-  if (s->shm > device_max_lds(p->device)) return cleanup(fail(BOTE_E_RANGE, "planet/client set too large for LDS"));
+  if (s->shm > device_max_lds(p->device)) return fail(BOTE_E_RANGE, "planet/client set too large for LDS");
   int nb = bote::eval_occupancy(n, false, s->bd, s->shm, keys != 0);
   s->grid = (uint32_t)(device_cus(p->device) * nb);
   s->xgrid = 32;
+  return BOTE_OK;
+}
 
-  // ---- fast path: quad layouts, column sums are computed on the device.
-  // `kernel` forces a path (tests, A/B timing; every path is exact); AUTO:
-  // the group kernel when eligible and >= 90 % lane utilisation.
-  const bool fair = has_score && rp && rp->min_fairness_fpaxos_improv != 0.0;
+// The group kernel's geometry at one workgroup size: the position table (n <=
+// 7) unless its LDS lowers the workgroups per CU, then as many client lines
+// per wave (<= 16) as keep that occupancy.  A workgroup shares the
+// client-quad matrix (CQT) among its waves, so at R = 128 larger workgroups
+// leave LDS for the client lines that 256-thread ones cannot hold (a step has
+// 7.7 distinct (p1, p2) on average at R=64 n=7, 4.0 at R=128 n=6; DESIGN.md
+// §4).  `f` is the candidate: a copy of the sweep's arguments, with gbins set.
+struct GGeo {
+  uint32_t bd = 0, grx = 0, gslots = 0, gqsh = 10;
+  int occ = 0;
+  size_t shm = 0;
+};
+static GGeo group_geometry(bote::FastArgs f, uint32_t n, bool def_obj, uint32_t bd, size_t max_lds) {
+  f.gbd = bd;
+  // qtab member planes (non-PERM kernels): one u32 per thread, so the
+  // plane stride 1 << gqsh must hold gbd * 4 bytes (bote_group.hip)
+  f.gqsh = 10;
+  while ((1u << f.gqsh) < f.gbd * 4) ++f.gqsh;
+  f.gslots = 0;
+  f.grx = 0;
+  if (bote::group_uses_lines(n)) {
+    const int occ_plain = bote::group_occupancy(f, n, bote::group_smem_bytes(f, n), def_obj);
+    f.grx = 1;
+    if (bote::group_occupancy(f, n, bote::group_smem_bytes(f, n), def_obj) < occ_plain) f.grx = 0;
+    const int occ0 = bote::group_occupancy(f, n, bote::group_smem_bytes(f, n), def_obj);
+    for (uint32_t sl = 16; sl >= 1; --sl) {
+      f.gslots = sl;
+      const size_t sh = bote::group_smem_bytes(f, n);
+      if (sh <= max_lds && bote::group_occupancy(f, n, sh, def_obj) >= occ0) break;
+      f.gslots = 0;
+    }
+  }
+  GGeo g;
+  g.bd = bd;
+  g.grx = f.grx;
+  g.gslots = f.gslots;
+  g.gqsh = f.gqsh;
+  g.shm = bote::group_smem_bytes(f, n);
+  g.occ = g.shm <= max_lds ? bote::group_occupancy(f, n, g.shm, def_obj) : 0;
+  return g;
+}
+
+// The best geometry over the candidate workgroup sizes (pick_group_geometry;
+// occ == 0: none fits): multiples of 256 threads up to 1024 (the extended key
+// set's kernels are bounded to bote::group_supports_keys' size).  Sizes of 6
+// or 10 waves put unequal wave counts on the 4 SIMDs of a CU (384 threads
+// measured 16-21 % slower than both neighbours; more waves per SIMD is not
+// the aim either: R=128 n=6 at 640 threads, 5 waves/SIMD, 369 ms vs 348 ms at
+// 256 threads, 2 waves/SIMD).  BOTE_GROUP_BD (env) forces one
+// size (A/B timing).
+static GGeo best_group_geometry(const bote::FastArgs& f, uint32_t n, bool def_obj, size_t max_lds) {
+  const char* bd_env = getenv("BOTE_GROUP_BD");
+  const uint32_t bd_only = bd_env ? (uint32_t)strtoul(bd_env, nullptr, 0) : 0u;
+  GGeo best;
+  for (uint32_t bd = 256; bd <= 1024; bd += 128) {
+    if (bd_only ? bd != bd_only : bd % 256 != 0) continue;
+    if (f.keys && !bote::group_supports_keys(n, bd)) continue;
+    const GGeo g = group_geometry(f, n, def_obj, bd, max_lds);
+    if (g.occ > 0 && pick_group_geometry(g.bd, g.occ, g.gslots, best.bd, best.occ, best.gslots)) best = g;
+  }
+  return best;
+}
+
+// Step 4 (a fast sweep): the group kernel when wanted and it fits: n >= 4,
+// positions fit 8 bits, and (AUTO) enough lane utilisation.
+static int sweep_plan_group(bote_sweep* s, const FastLimits& lim, bool compiled_objs, int kernel) {
+  const bote_planet* p = s->p;
+  const uint32_t n = s->n, ns = s->ns, nc = s->nc;
+  bote::FastArgs& f = s->fargs;
+  bool want_group = n >= 4 && ns <= 256 && group_utilisation(ns, n) >= 0.9;
+  if (kernel != BOTE_KERNEL_AUTO) want_group = n >= 4 && ns <= 256 && kernel == BOTE_KERNEL_GROUP;
+  if (kernel == BOTE_KERNEL_GROUP && !want_group) return fail(BOTE_E_ARG, "group kernel needs n >= 4");
+  if (!s->fast || !want_group) return BOTE_OK;
+  auto lt = low_table(ns - (n - 3));
+#ifdef BOTE_DEBUG
+  f.lowtab_n = lt.size();
+#endif
+  // (64 padding entries: a step's lanes read the table past a group's
+  // last row without a clamp; those lanes hold no config)
+  lt.resize(lt.size() + 64, 0u);
+  if (s->lowtab.alloc(std::max<size_t>(lt.size(), 1) * 4) != hipSuccess)
+    return fail(BOTE_E_NOMEM, "hipMalloc group low table");
+  if (!lt.empty() && hipMemcpy(s->lowtab.p, lt.data(), lt.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
+    return fail(BOTE_E_DEVICE, "upload group low table");
+  f.lowtab = s->lowtab.as<uint32_t>();
+  // the objective set compiled into the DEF kernels (bote.py
+  // DEFAULT_OBJECTIVES; with the extended keys, CONFIG5_OBJECTIVES)
+  s->def_obj = compiled_objs && f.want_score;
+  // the member-binned client loop on the base key set: bench-shaped
+  // sweeps (server identity, digest, F1F2: the SI kernels) with >= 32
+  // clients, where the bin fields cannot overflow (R=64 n=7: 14.26 vs
+  // 14.89 ms for the register lookups, profiles/r04c; R=128 n=6: 168 vs
+  // 180 ms, round 3)
+  f.gbins = !f.keys && s->def_obj && bote::group_uses_lines(n) && nc >= BOTE_GBINS_MIN_NC && lim.bins_ok &&
+            f.srv_identity && f.want_digest && f.ft_metric == 2;
+  const GGeo best = best_group_geometry(f, n, s->def_obj, device_max_lds(p->device));
+  if (best.occ > 0 && (!f.keys || s->def_obj)) {
+    f.gbd = best.bd;
+    f.grx = best.grx;
+    f.gslots = best.gslots;
+    f.gqsh = best.gqsh;
+    s->group = true;
+    s->fshm = best.shm;
+    s->fgrid = (uint32_t)(device_cus(p->device) * best.occ);
+  }
+  return BOTE_OK;
+}
+
+// The fast kernels' arguments (s->fargs): the client-quad layouts, uploaded
+// (column sums are computed on the device), and the host plan copied in.
+static int fill_fast_args(bote_sweep* s, const uint32_t* servers, const uint32_t* clients, const FastLimits& lim) {
+  const bote_planet* p = s->p;
+  const EvalArgs& a = s->args;
+  const uint32_t ns = s->ns, nc = s->nc;
+  bote::FastArgs& f = s->fargs;
+  f = bote::FastArgs{};
+  std::vector<uint32_t> ident(p->R);
+  for (uint32_t i = 0; i < p->R; ++i) ident[i] = i;
+  bool cli_ident = nc == p->R && std::equal(clients, clients + nc, ident.begin());
+  uint32_t cq_quads = 0, rq_quads = 0, cq_stride = 0, rq_stride = 0;
+  auto cq = quad_layout(p->lat.data(), p->R, clients, nc, bote::LAT_SHIFT, cq_quads, cq_stride);
+  std::vector<uint16_t> rq;
+  if (!cli_ident) rq = quad_layout(p->lat.data(), p->R, ident.data(), p->R, bote::LAT_SHIFT, rq_quads, rq_stride);
+  if (s->cqt.alloc(cq.size() * 2) != hipSuccess || (!cli_ident && s->rqt.alloc(rq.size() * 2) != hipSuccess) ||
+      s->queue.alloc(QUEUE_CAP * 8) != hipSuccess || s->qcount.alloc(16) != hipSuccess)
+    return fail(BOTE_E_NOMEM, "hipMalloc fast-path buffers");
+  if (hipMemcpy(s->cqt.p, cq.data(), cq.size() * 2, hipMemcpyHostToDevice) != hipSuccess ||
+      (!cli_ident && hipMemcpy(s->rqt.p, rq.data(), rq.size() * 2, hipMemcpyHostToDevice) != hipSuccess))
+    return fail(BOTE_E_DEVICE, "upload fast-path layouts");
+  f.cqt = s->cqt.as<uint2>();
+  f.rqt = cli_ident ? s->cqt.as<uint2>() : s->rqt.as<uint2>();
+  f.rq_separate = cli_ident ? 0 : 1;
+  f.R = p->R;
+  f.cq_quads = cq_quads;
+  f.rq_quads = cli_ident ? cq_quads : rq_quads;
+  f.cq_stride = cq_stride;
+  f.rq_stride = cli_ident ? cq_stride : rq_stride;
+  f.srv = s->srv.as<uint32_t>();
+  f.ns = ns;
+  f.keys = a.keys;
+  f.srv_identity = 1;
+  for (uint32_t i = 0; i < ns; ++i) f.srv_identity &= servers[i] == i;
+  f.nc = nc;
+  f.binom = s->binom.as<uint64_t>();
+  f.s2_flush = lim.s2_flush;
+  f.g_flush = lim.g_flush;
+  f.k_flush = lim.k_flush;
+  f.s32 = lim.s32 ? 1u : 0u;
+  f.v32 = lim.v32 ? 1u : 0u;
+  f.want_score = a.want_score;
+  f.p_fmean = a.p_fmean;
+  f.p_emean = a.p_emean;
+  f.ft_metric = a.ft_metric;
+  const ScoreBands sb = score_bands(a.p_fmean, a.p_emean, nc);
+  f.p_int = sb.p_int;
+  f.p1i = sb.p1i;
+  f.p2i = sb.p2i;
+  f.m1_lo = sb.m1_lo;
+  f.m1_hi = sb.m1_hi;
+  f.m2_lo = sb.m2_lo;
+  f.m2_hi = sb.m2_hi;
+  f.n_obj = a.n_obj;
+  for (int o = 0; o < bote::MAXOBJ; ++o) {
+    f.obj_kind[o] = a.obj_kind[o];
+    f.obj_slot[o] = a.obj_slot[o];
+  }
+  f.K = s->K;
+  f.out_counters = a.out_counters;
+  f.want_digest = a.want_digest;
+  f.queue = s->queue.as<uint64_t>();
+  f.queue_count = s->qcount.as<unsigned long long>();
+  f.queue_cap = QUEUE_CAP;
+  return BOTE_OK;
+}
+
+// Step 3: the fast path.  Decides s->fast, fills s->fargs and sizes the fast
+// kernel's launch, then plans the group kernel (step 4).  `kernel` forces a
+// path (tests, A/B timing; every path is exact); AUTO: the group kernel when
+// eligible and >= 90 % lane utilisation.
+static int sweep_plan_fast(bote_sweep* s, const uint32_t* servers, const uint32_t* clients, bool fair, int kernel) {
+  const bote_planet* p = s->p;
+  const EvalArgs& a = s->args;
+  const uint32_t n = s->n, ns = s->ns, nc = s->nc, keys = a.keys;
   s->fast = fast_eligible(p->lat.data(), p->R, servers, ns, nc, fair) && kernel != BOTE_KERNEL_GENERIC;
   if (kernel != BOTE_KERNEL_AUTO && kernel != BOTE_KERNEL_GENERIC && !s->fast)
-    return cleanup(fail(BOTE_E_ARG, "the fast/group kernel is not eligible for this planet and lists"));
-  // the extended key set runs on the group kernel (n = 4..7, the default
-  // objectives first) or on the generic kernel
-  // (config 5's objective set, compiled into the group kernel: bote.py
-  // CONFIG5_OBJECTIVES = the default five, MEAN tt1, MEAN tw2, MEAN fl1)
-  bool keys_def = n_obj == 8 && has_score;
-  static const uint32_t dkk[8] = {BOTE_OBJ_SCORE, BOTE_OBJ_MEAN, BOTE_OBJ_MEAN, BOTE_OBJ_COV,
-                                  BOTE_OBJ_MEAN,  BOTE_OBJ_MEAN, BOTE_OBJ_MEAN, BOTE_OBJ_MEAN};
-  static const uint32_t dss[8] = {0, BOTE_SLOT_AF1, BOTE_SLOT_FF1, BOTE_SLOT_AF1,
-                                  BOTE_SLOT_E, BOTE_SLOT_TT1, BOTE_SLOT_TW2, BOTE_SLOT_FL1};
-  for (uint32_t o = 0; keys_def && o < 8; ++o)
-    keys_def = objs[o].kind == dkk[o] && (dkk[o] == BOTE_OBJ_SCORE || objs[o].slot == dss[o]);
-  // (the group kernel's extended keys use 32-bit moments: every sum of
-  // squares nc * (2 max)^2 and 3 nc max must fit their 32/24 bits)
-  uint64_t maxlat_all = 0;
-  for (auto v : p->lat) maxlat_all = std::max<uint64_t>(maxlat_all, v);
-  // (and its member bins: a client count below 2^8, a sum of nc keys
-  // (latency << 4 | member) below 2^24 and two squared keys below 2^32,
-  // bote_group.hip)
-  const bool keys32 = (uint64_t)nc * (2 * maxlat_all) * (2 * maxlat_all) < (1ull << 32) &&
-                      (uint64_t)nc * maxlat_all < (1ull << 16) &&  // (packed member-pair bins)
-                      3ull * nc * maxlat_all < (1ull << 24) && nc < 256 &&
-                      (uint64_t)nc * (16 * maxlat_all + 15) < (1ull << 24) &&
-                      2 * (16 * maxlat_all + 15) * (16 * maxlat_all + 15) < (1ull << 32);
+    return fail(BOTE_E_ARG, "the fast/group kernel is not eligible for this planet and lists");
+  // the extended key set runs on the group kernel (n = 4..7, config 5's
+  // objective set, compiled into it, and moments that fit its 32-bit
+  // arithmetic: FastLimits::keys32) or on the generic kernel
+  const bool compiled_objs = is_compiled_objective_set(a.obj_kind, a.obj_slot, s->n_obj, keys);
+  const FastLimits lim = fast_limits(p->lat.data(), p->R, nc, n);
   if (keys && s->fast &&
-      (!bote::group_supports_keys(n, bote::GROUP_XK_MAX_BD) || !keys_def || !keys32 || kernel == BOTE_KERNEL_FAST)) {
+      (!bote::group_supports_keys(n, bote::GROUP_XK_MAX_BD) || !compiled_objs || !lim.keys32 ||
+       kernel == BOTE_KERNEL_FAST)) {
     if (kernel == BOTE_KERNEL_FAST || kernel == BOTE_KERNEL_GROUP)
-      return cleanup(fail(BOTE_E_ARG, "the extended key set runs on the group kernel (n = 4..7, config 5's "
-                                      "objectives) or the generic kernel"));
+      return fail(BOTE_E_ARG, "the extended key set runs on the group kernel (n = 4..7, config 5's "
+                              "objectives) or the generic kernel");
     s->fast = false;
   }
-  if (s->fast) {
-    bote::FastArgs& f = s->fargs;
-    f = bote::FastArgs{};
-    std::vector<uint32_t> ident(p->R);
-    for (uint32_t i = 0; i < p->R; ++i) ident[i] = i;
-    bool cli_ident = nc == p->R && std::equal(clients, clients + nc, ident.begin());
-    uint32_t cq_quads = 0, rq_quads = 0, cq_stride = 0, rq_stride = 0;
-    auto cq = quad_layout(p->lat.data(), p->R, clients, nc, bote::LAT_SHIFT, cq_quads, cq_stride);
-    std::vector<uint16_t> rq;
-    if (!cli_ident) rq = quad_layout(p->lat.data(), p->R, ident.data(), p->R, bote::LAT_SHIFT, rq_quads, rq_stride);
-    if (s->cqt.alloc(cq.size() * 2) != hipSuccess || (!cli_ident && s->rqt.alloc(rq.size() * 2) != hipSuccess) ||
-        s->queue.alloc(QUEUE_CAP * 8) != hipSuccess || s->qcount.alloc(16) != hipSuccess)
-      return cleanup(fail(BOTE_E_NOMEM, "hipMalloc fast-path buffers"));
-    if (hipMemcpy(s->cqt.p, cq.data(), cq.size() * 2, hipMemcpyHostToDevice) != hipSuccess ||
-        (!cli_ident && hipMemcpy(s->rqt.p, rq.data(), rq.size() * 2, hipMemcpyHostToDevice) != hipSuccess))
-      return cleanup(fail(BOTE_E_DEVICE, "upload fast-path layouts"));
-    f.cqt = s->cqt.as<uint2>();
-    f.rqt = cli_ident ? s->cqt.as<uint2>() : s->rqt.as<uint2>();
-    f.rq_separate = cli_ident ? 0 : 1;
-    f.R = p->R;
-    f.cq_quads = cq_quads;
-    f.rq_quads = cli_ident ? cq_quads : rq_quads;
-    f.cq_stride = cq_stride;
-    f.rq_stride = cli_ident ? cq_stride : rq_stride;
-    f.srv = s->srv.as<uint32_t>();
-    f.ns = ns;
-    f.keys = keys;
-    f.srv_identity = 1;
-    for (uint32_t i = 0; i < ns; ++i) f.srv_identity &= servers[i] == i;
-    f.nc = nc;
-    f.binom = s->binom.as<uint64_t>();
-    uint32_t maxlat = 0;
-    for (auto v : p->lat) maxlat = std::max<uint32_t>(maxlat, v);
-    const uint64_t amax = 2ull * maxlat, per_quad = 4 * amax * amax;
-    f.s2_flush = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(1u << 20, per_quad ? 0xFFFFFFFFull / per_quad : 1u << 20));
-    // packed-u16 sums (group kernel): each half gains <= 2 * amax per quad
-    const uint64_t s1_flush = amax ? 0xFFFFull / (2 * amax) : 1u << 20;
-    f.g_flush = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(f.s2_flush, s1_flush));
-    // extended keys: squares of the packed keys (latency << 4 | member), two
-    // per dot2 into 32 bits (keys32 below requires 2 key^2 < 2^32)
-    const uint64_t kmax = 16ull * maxlat + 15, kq = 4 * kmax * kmax;
-    f.k_flush = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(1u << 20, 0xFFFFFFFFull / kq));
-    // every slot's sum of squares below 2^32 (a value is at most a latency
-    // plus a quorum latency, 2 max, over nc >= N clients): the bench-shaped
-    // group kernels keep the moments in 32 bits (bote_group.hip S32)
-    // (and the FPaxos moments' 24-bit multiplies: column sum + S1 <= 3 nc max < 2^24)
-    f.s32 = (uint64_t)std::max(nc, n) * amax * amax < (1ull << 32) && 3ull * nc * maxlat < (1ull << 24) ? 1u : 0u;
-    // and every V = cnt s2 - s1^2 in 32 bits: V = sum over pairs of
-    // (x_i - x_j)^2 <= (cnt / 2)^2 (2 max)^2 = cnt^2 max^2 for values x in
-    // [0, 2 max], so cnt max < 2^16 suffices (the kernels compute V mod 2^32
-    // from 32-bit products: exact when V < 2^32).  Round 5 asked cnt^2 (2 max)^2
-    // < 2^32, which config 5 (128 clients) missed.
-    f.v32 = f.s32 && (uint64_t)std::max(nc, n) * maxlat < (1ull << 16) ? 1u : 0u;
-    f.want_score = a.want_score;
-    f.p_fmean = a.p_fmean;
-    f.p_emean = a.p_emean;
-    f.ft_metric = a.ft_metric;
-    auto integral = [](double x) { return x == (double)(int64_t)x && x > -1e12 && x < 1e12; };
-    f.p_int = integral(a.p_fmean) && integral(a.p_emean) ? 1 : 0;
-    f.p1i = f.p_int ? (int64_t)a.p_fmean * (int64_t)nc : 0;
-    f.p2i = f.p_int ? (int64_t)a.p_emean * (int64_t)nc : 0;
-    auto band = [&](double p, int64_t pi, int32_t& lo, int32_t& hi) {
-      const double t = p * (double)nc;
-      const double l = f.p_int ? (double)pi : std::floor(t) - 1.0, h = f.p_int ? (double)pi : std::ceil(t) + 1.0;
-      const double cap = 2147483647.0;  // D = a difference of two sums below 2^21
-      lo = (int32_t)std::max(-cap, std::min(cap, l));
-      hi = (int32_t)std::max(-cap, std::min(cap, h));
-    };
-    band(a.p_fmean, f.p1i, f.m1_lo, f.m1_hi);
-    band(a.p_emean, f.p2i, f.m2_lo, f.m2_hi);
-    f.n_obj = a.n_obj;
-    for (int o = 0; o < bote::MAXOBJ; ++o) {
-      f.obj_kind[o] = a.obj_kind[o];
-      f.obj_slot[o] = a.obj_slot[o];
-    }
-    f.K = K;
-    f.out_counters = a.out_counters;
-    f.want_digest = a.want_digest;
-    f.queue = s->queue.as<uint64_t>();
-    f.queue_count = s->qcount.as<unsigned long long>();
-    f.queue_cap = QUEUE_CAP;
+  if (!s->fast) return BOTE_OK;
+  int rc;
+  if ((rc = fill_fast_args(s, servers, clients, lim))) return rc;
+  bote::FastArgs& f = s->fargs;
 #ifdef BOTE_DEBUG
-    if (s->dbg.alloc(16) != hipSuccess || hipMemset(s->dbg.p, 0, 16) != hipSuccess)
-      return cleanup(fail(BOTE_E_NOMEM, "debug flag"));
-    f.dbg_flag = s->dbg.as<unsigned int>();
+  if (s->dbg.alloc(16) != hipSuccess || hipMemset(s->dbg.p, 0, 16) != hipSuccess)
+    return fail(BOTE_E_NOMEM, "debug flag");
+  f.dbg_flag = s->dbg.as<unsigned int>();
 #endif
 #ifdef BOTE_PATHSTATS
-    if (s->pstats.alloc(64 * 8) != hipSuccess || hipMemset(s->pstats.p, 0, 64 * 8) != hipSuccess)
-      return cleanup(fail(BOTE_E_NOMEM, "path counters"));
-    f.pstats = s->pstats.as<unsigned long long>();
+  if (s->pstats.alloc(64 * 8) != hipSuccess || hipMemset(s->pstats.p, 0, 64 * 8) != hipSuccess)
+    return fail(BOTE_E_NOMEM, "path counters");
+  f.pstats = s->pstats.as<unsigned long long>();
 #endif
 #ifdef BOTE_ABLATION
-    const char* abl = getenv("BOTE_ABLATE");  // timing-diagnostics builds only
-    f.ablate = abl ? (uint32_t)strtoul(abl, nullptr, 0) : 0u;
+  const char* abl = getenv("BOTE_ABLATE");  // timing-diagnostics builds only
+  f.ablate = abl ? (uint32_t)strtoul(abl, nullptr, 0) : 0u;
 #endif
-    s->fshm = bote::fast_smem_bytes(f, n);
-    if (s->fshm > device_max_lds(p->device)) {
-      s->fast = false;
-    } else {
-      s->fgrid = (uint32_t)(device_cus(p->device) * bote::fast_occupancy(n, s->fshm));
-    }
-    // group kernel: n >= 4, positions fit 8 bits, enough lane utilisation
-    bool want_group = n >= 4 && ns <= 256 && group_utilisation(ns, n) >= 0.9;
-    if (kernel != BOTE_KERNEL_AUTO) want_group = n >= 4 && ns <= 256 && kernel == BOTE_KERNEL_GROUP;
-    if (kernel == BOTE_KERNEL_GROUP && !want_group) return cleanup(fail(BOTE_E_ARG, "group kernel needs n >= 4"));
-    if (s->fast && want_group) {
-      auto lt = low_table(ns - (n - 3));
-#ifdef BOTE_DEBUG
-      f.lowtab_n = lt.size();
-#endif
-      // (64 padding entries: a step's lanes read the table past a group's
-      // last row without a clamp; those lanes hold no config)
-      lt.resize(lt.size() + 64, 0u);
-      if (s->lowtab.alloc(std::max<size_t>(lt.size(), 1) * 4) != hipSuccess)
-        return cleanup(fail(BOTE_E_NOMEM, "hipMalloc group low table"));
-      if (!lt.empty() && hipMemcpy(s->lowtab.p, lt.data(), lt.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
-        return cleanup(fail(BOTE_E_DEVICE, "upload group low table"));
-      f.lowtab = s->lowtab.as<uint32_t>();
-      // workgroup size: 256 threads (4 waves).  Larger workgroups (which
-      // share the client-quad matrix, so R = 128 fits more waves per CU) were
-      // measured slower: R=128 n=6 at 640 threads, 5 waves/SIMD, 369 ms vs
-      // 348 ms at 256 threads, 2 waves/SIMD.
-      // bote.py DEFAULT_OBJECTIVES: SCORE, MEAN af1, MEAN ff1, COV af1, MEAN e
-      static const uint32_t dk[5] = {BOTE_OBJ_SCORE, BOTE_OBJ_MEAN, BOTE_OBJ_MEAN, BOTE_OBJ_COV, BOTE_OBJ_MEAN};
-      static const uint32_t ds[5] = {0, BOTE_SLOT_AF1, BOTE_SLOT_FF1, BOTE_SLOT_AF1, BOTE_SLOT_E};
-      s->def_obj = (keys ? keys_def : n_obj == 5) && f.want_score;
-      for (uint32_t o = 0; s->def_obj && o < 5; ++o)
-        s->def_obj = objs[o].kind == dk[o] && (dk[o] == BOTE_OBJ_SCORE || objs[o].slot == ds[o]);
-      // One geometry per candidate workgroup size: the position table (n <= 7)
-      // unless its LDS lowers the workgroups per CU, then as many client
-      // lines per wave (<= 16) as keep that occupancy.  A workgroup shares the
-      // client-quad matrix (CQT) among its waves, so at R = 128 larger
-      // workgroups leave LDS for the client lines that 256-thread ones cannot
-      // hold (a step has 7.7 distinct (p1, p2) on average at R=64 n=7, 4.0 at
-      // R=128 n=6).  pick_group_geometry keeps the best.
-      // the member-binned client loop on the base key set: bench-shaped
-      // sweeps (server identity, digest, F1F2: the SI kernels) with >= 32
-      // clients, where the bin fields cannot overflow (R=64 n=7: 14.26 vs
-      // 14.89 ms for the register lookups, profiles/r04c; R=128 n=6: 168 vs
-      // 180 ms, round 3)
-      f.gbins = !keys && s->def_obj && bote::group_uses_lines(n) && nc >= BOTE_GBINS_MIN_NC && nc < 256 && f.srv_identity &&
-                f.want_digest && f.ft_metric == 2 && (uint64_t)nc * (16ull * maxlat + 15) < (1ull << 24) &&
-                (uint64_t)nc * maxlat < (1ull << 16) &&  // (packed member-pair bins)
-                2 * (16ull * maxlat + 15) * (16ull * maxlat + 15) < (1ull << 32);
-      struct GGeo {
-        uint32_t bd = 0, grx = 0, gslots = 0, gqsh = 10;
-        int occ = 0;
-        size_t shm = 0;
-      };
-      auto geometry = [&](uint32_t bd) {
-        GGeo g;
-        g.bd = bd;
-        f.gbd = bd;
-        // qtab member planes (non-PERM kernels): one u32 per thread, so the
-        // plane stride 1 << gqsh must hold gbd * 4 bytes (bote_group.hip)
-        f.gqsh = 10;
-        while ((1u << f.gqsh) < f.gbd * 4) ++f.gqsh;
-        f.gslots = 0;
-        f.grx = 0;
-        if (bote::group_uses_lines(n)) {
-          const int occ_plain = bote::group_occupancy(f, n, bote::group_smem_bytes(f, n), s->def_obj);
-          f.grx = 1;
-          if (bote::group_occupancy(f, n, bote::group_smem_bytes(f, n), s->def_obj) < occ_plain) f.grx = 0;
-          const int occ0 = bote::group_occupancy(f, n, bote::group_smem_bytes(f, n), s->def_obj);
-          for (uint32_t sl = 16; sl >= 1; --sl) {
-            f.gslots = sl;
-            const size_t sh = bote::group_smem_bytes(f, n);
-            if (sh <= device_max_lds(p->device) && bote::group_occupancy(f, n, sh, s->def_obj) >= occ0) break;
-            f.gslots = 0;
-          }
-        }
-        g.grx = f.grx;
-        g.gslots = f.gslots;
-        g.gqsh = f.gqsh;
-        g.shm = bote::group_smem_bytes(f, n);
-        g.occ = g.shm <= device_max_lds(p->device) ? bote::group_occupancy(f, n, g.shm, s->def_obj) : 0;
-        return g;
-      };
-      // candidates: multiples of 256 threads up to 1024 (the extended key
-      // set's kernels are bounded to bote::group_supports_keys' size).  Sizes
-      // of 6 or 10 waves put unequal wave counts on the 4 SIMDs of a CU
-      // (384 threads measured 16-21 % slower than both neighbours).
-      // BOTE_GROUP_BD (env) forces one size (A/B timing).
-      const char* bd_env = getenv("BOTE_GROUP_BD");
-      const uint32_t bd_only = bd_env ? (uint32_t)strtoul(bd_env, nullptr, 0) : 0u;
-      GGeo best;
-      for (uint32_t bd = 256; bd <= 1024; bd += 128) {
-        if (bd_only ? bd != bd_only : bd % 256 != 0) continue;
-        if (keys && !bote::group_supports_keys(n, bd)) continue;
-        const GGeo g = geometry(bd);
-        if (g.occ > 0 && bote::host::pick_group_geometry(g.bd, g.occ, g.gslots, best.bd, best.occ, best.gslots)) best = g;
-      }
-      if (best.occ > 0 && (!keys || s->def_obj)) {
-        f.gbd = best.bd;
-        f.grx = best.grx;
-        f.gslots = best.gslots;
-        f.gqsh = best.gqsh;
-        s->group = true;
-        s->fshm = best.shm;
-        s->fgrid = (uint32_t)(device_cus(p->device) * best.occ);
-      }
-    }
+  s->fshm = bote::fast_smem_bytes(f, n);
+  if (s->fshm > device_max_lds(p->device)) {
+    s->fast = false;
+  } else {
+    s->fgrid = (uint32_t)(device_cus(p->device) * bote::fast_occupancy(n, s->fshm));
   }
-  // the fast (non-group) kernel does not compute the extended key set
-  if (keys && s->fast && !s->group) s->fast = false;
+  return sweep_plan_group(s, lim, compiled_objs, kernel);
+}
+
+// Step 5: the per-block lists, the merge buffers, the result block and the
+// events.
+static int sweep_alloc_workspace(bote_sweep* s) {
+  const uint32_t n_obj = s->n_obj;
   // the generic path may also run on a fast sweep (overflow recompute)
   const uint32_t lists = s->fast ? std::max(s->grid, s->fgrid + s->xgrid) : s->grid;
   size_t top_bytes = (size_t)lists * std::max<uint32_t>(n_obj, 1) * bote::KP * 16;
   size_t tmp_bytes = (size_t)((lists + 7) / 8) * std::max<uint32_t>(n_obj, 1) * bote::KP * 16;
   if (s->top.alloc(top_bytes) != hipSuccess || s->tmp0.alloc(tmp_bytes) != hipSuccess ||
       s->tmp1.alloc(tmp_bytes) != hipSuccess || s->result.alloc(s->result_bytes()) != hipSuccess)
-    return cleanup(fail(BOTE_E_NOMEM, "hipMalloc sweep workspace"));
+    return fail(BOTE_E_NOMEM, "hipMalloc sweep workspace");
   if (s->fast && (s->top_alt.alloc((size_t)s->grid * std::max<uint32_t>(n_obj, 1) * bote::KP * 16) != hipSuccess ||
                   s->counters_alt.alloc(16) != hipSuccess))
-    return cleanup(fail(BOTE_E_NOMEM, "hipMalloc overflow fallback workspace"));
-  a.out_top = n_obj ? s->top.as<Rec>() : nullptr;
-  s->fargs.out_top = a.out_top;
+    return fail(BOTE_E_NOMEM, "hipMalloc overflow fallback workspace");
+  s->args.out_top = n_obj ? s->top.as<Rec>() : nullptr;
+  s->fargs.out_top = s->args.out_top;
   if (hipEventCreate(&s->ev0) != hipSuccess || hipEventCreate(&s->ev1) != hipSuccess ||
       hipEventCreateWithFlags(&s->done, hipEventDisableTiming) != hipSuccess)
-    return cleanup(fail(BOTE_E_DEVICE, "hipEventCreate"));
+    return fail(BOTE_E_DEVICE, "hipEventCreate");
+  return BOTE_OK;
+}
+
+int bote_sweep_create_keys(const bote_planet* p, const uint32_t* servers, uint32_t ns, const uint32_t* clients,
+                           uint32_t nc, uint32_t n, const bote_objective* objs, uint32_t n_obj, uint32_t K,
+                           const bote_ranking_params* rp, int digest, int kernel, uint32_t keys, bote_sweep** out) {
+  DevGuard dev_guard;  // the caller's current device is restored on return
+  int rc;
+  bool has_score = false;
+  if ((rc = sweep_check_args(p, servers, ns, clients, nc, n, objs, n_obj, K, rp, kernel, keys, out, has_score)))
+    return rc;
+  HIP_TRY(hipSetDevice(p->device));
+  auto* s = new bote_sweep();
+  auto cleanup = [&](int code) {
+    bote_sweep_destroy(s);
+    return code;
+  };
+  s->p = p;
+  s->n = n;
+  s->ns = ns;
+  s->nc = nc;
+  s->n_obj = n_obj;
+  s->K = K;
+  if ((rc = sweep_upload_lists(s, servers, clients, objs, rp, has_score, digest, keys))) return cleanup(rc);
+  const bool fair = has_score && rp && rp->min_fairness_fpaxos_improv != 0.0;
+  if ((rc = sweep_plan_fast(s, servers, clients, fair, kernel))) return cleanup(rc);
+  // the fast (non-group) kernel does not compute the extended key set
+  if (keys && s->fast && !s->group) s->fast = false;
+  if ((rc = sweep_alloc_workspace(s))) return cleanup(rc);
   *out = s;
   return BOTE_OK;
 }
@@ -1082,21 +1091,8 @@ static int sweep_chunks(bote_sweep* s, uint64_t rb, uint64_t re, hipStream_t st,
       HIP_TRY(hipMemcpyAsync(c->dev.p, c->host.data(), c->host.size() * 8, hipMemcpyHostToDevice, st));
       // each chunk's first group (FastArgs::wstate): the kernel starts a
       // chunk with two loads instead of a device unrank
-      const uint32_t F = s->n - 3;
-      if (F <= 16) {
-        c->state.assign((size_t)c->n * 4, 0);
-        std::vector<uint32_t> p(s->n);
-        for (uint32_t i = 0; i < c->n; ++i) {
-          if (!colex_unrank(c->host[i], s->n, s->ns, p.data())) return fail(BOTE_E_ARG, "chunk rank out of range");
-          uint64_t base = 0, b[2] = {0, 0};
-          for (uint32_t k = 0; k < F; ++k) {
-            base += binom_u64(p[3 + k], k + 4);
-            b[k / 8] |= (uint64_t)p[3 + k] << (8 * (k % 8));
-          }
-          c->state[4 * (size_t)i] = base;
-          c->state[4 * (size_t)i + 1] = b[0];
-          c->state[4 * (size_t)i + 2] = b[1];
-        }
+      if (s->n - 3 <= 16) {
+        if (!chunk_states(c->host.data(), c->n, s->n, s->ns, c->state)) return fail(BOTE_E_ARG, "chunk rank out of range");
         if (c->sdev.alloc(c->state.size() * 8) != hipSuccess) return fail(BOTE_E_NOMEM, "hipMalloc chunk states");
         HIP_TRY(hipMemcpyAsync(c->sdev.p, c->state.data(), c->state.size() * 8, hipMemcpyHostToDevice, st));
       }
@@ -1176,9 +1172,7 @@ static int launch_generic(bote_sweep* s, uint64_t rb, uint64_t re, hipStream_t s
   EvalArgs a = s->args;
   a.rb = rb;
   a.re = re;
-  const uint64_t count = re - rb;
-  const uint64_t G = (uint64_t)s->grid * s->bd;
-  a.runlen = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(32, count / (G * 8)));
+  a.runlen = sweep_runlen(re - rb, s->grid, s->bd);
   HIP_TRY(hipMemsetAsync(s->counters.p, 0, 16, st));
   hipEvent_t *e0 = nullptr, *e1 = nullptr;
   int rc;
@@ -1193,30 +1187,12 @@ static int launch_generic(bote_sweep* s, uint64_t rb, uint64_t re, hipStream_t s
 
 // The top-K seed of a group launch over [rb, re) (launch_fast_path): sets
 // f.tseed, or leaves it null when the range is too small to sample.
-// sample steps per wave on a full range (r03v A/B: 8 vs 1, kernel -1.6 %, 1/8
-// shard -5 %; r05g: 4 and 8 give the same R=64 n=7 step, 14.15-14.17 vs
-// 14.16-14.25 ms, and 4 halves the sample launch: 0.14 vs 0.18 ms outside the kernel)
-constexpr uint32_t SEED_STEPS = 4;
+// The sample plan (how many one-step chunks, where) is bote_host.cpp's
+// sample_count / sample_starts.
 static int sample_seed(bote_sweep* s, bote::FastArgs& f, uint64_t rb, uint64_t re, hipStream_t st) {
   const uint32_t nwaves = s->fgrid * (s->fargs.gbd / 64);
-  const uint32_t base = std::min<uint32_t>(4096, nwaves);
-  // SEED_STEPS one-step chunks per wave, disjoint and at most 1/8 of the
-  // range.  (Chunks of 8 consecutive steps, 4,096 of them, measured slower:
-  // kernel 15.52 vs 15.35 ms, their K least minima are a looser bound, r03x.)
-  const uint64_t fit = (re - rb) / (64 * 8);
-  const uint32_t ssteps = 1;  // one step per sample chunk (one group precompute each)
-  // sample steps per wave: SEED_STEPS on a full sweep; a shard's launch
-  // scales them by sqrt(its share of the rank space), rounded up: the sample
-  // costs ~ steps, the block merges it saves
-  // ~ range / steps, so the best count grows as sqrt(range).  r05g, R=64 n=7
-  // shards, 8 scaled (8 / 3 / 1 steps) against 8 fixed: 1/8 shard 2.089 vs
-  // 2.125 ms per step, 1/64 0.492 vs 0.531 ms
-  const double share = (double)(re - rb) / (double)binom_u64(s->ns, s->n);
-  const uint32_t steps =
-      (uint32_t)std::max(1.0, std::min((double)SEED_STEPS, std::ceil(SEED_STEPS * std::sqrt(share) - 1e-9)));
-  const uint32_t nsamp = (uint32_t)std::min<uint64_t>(
-      {(uint64_t)base * std::max<uint32_t>(1, steps), std::max<uint64_t>(base, fit / ssteps), 65536});
-  if (nsamp < s->K || re - rb < (uint64_t)nsamp * ssteps * 64 * 8) return BOTE_OK;
+  const uint32_t nsamp = sample_count(rb, re, binom_u64(s->ns, s->n), nwaves, s->K);
+  if (!nsamp) return BOTE_OK;
   auto key = std::make_pair(rb, re);
   auto it = s->samples.find(key);
   if (it == s->samples.end()) {
@@ -1225,26 +1201,11 @@ static int sample_seed(bote_sweep* s, bote::FastArgs& f, uint64_t rb, uint64_t r
       HIP_TRY(hipStreamSynchronize(st));
       s->samples.clear();
     }
+    if (s->n - 3 > 16) return BOTE_OK;
     auto c = std::make_unique<bote_sweep::Chunks>();
     c->n = nsamp;
-    c->host.resize(nsamp);
-    c->state.assign((size_t)nsamp * 4, 0);
-    std::vector<uint32_t> p(s->n);
-    const uint32_t F = s->n - 3;
-    if (F > 16) return BOTE_OK;
-    for (uint32_t i = 0; i < nsamp; ++i) {
-      const uint64_t b = rb + (uint64_t)(((unsigned __int128)(re - rb - 64) * i) / nsamp);
-      c->host[i] = b;
-      if (!colex_unrank(b, s->n, s->ns, p.data())) return fail(BOTE_E_ARG, "sample rank out of range");
-      uint64_t base = 0, w[2] = {0, 0};
-      for (uint32_t k = 0; k < F; ++k) {
-        base += binom_u64(p[3 + k], k + 4);
-        w[k / 8] |= (uint64_t)p[3 + k] << (8 * (k % 8));
-      }
-      c->state[4 * (size_t)i] = base;
-      c->state[4 * (size_t)i + 1] = w[0];
-      c->state[4 * (size_t)i + 2] = w[1];
-    }
+    c->host = sample_starts(rb, re, nsamp);
+    if (!chunk_states(c->host.data(), nsamp, s->n, s->ns, c->state)) return fail(BOTE_E_ARG, "sample rank out of range");
     if (c->dev.alloc(c->host.size() * 8) != hipSuccess || c->sdev.alloc(c->state.size() * 8) != hipSuccess)
       return fail(BOTE_E_NOMEM, "hipMalloc sample chunks");
     HIP_TRY(hipMemcpyAsync(c->dev.p, c->host.data(), c->host.size() * 8, hipMemcpyHostToDevice, st));
@@ -1265,7 +1226,7 @@ static int sample_seed(bote_sweep* s, bote::FastArgs& f, uint64_t rb, uint64_t r
   fs.wchunks = c->dev.as<uint64_t>();
   fs.wstate = c->sdev.as<uint64_t>();
   fs.nwchunks = nsamp;
-  fs.ssteps = ssteps;
+  fs.ssteps = 1;  // one step per sample chunk (one group precompute each)
   fs.smin_wave = slots == nwaves && slots != nsamp ? 1u : 0u;
   fs.wctr = f.wctr + 256;  // the sample launch's ticket shards
   HIP_TRY(bote::launch_group(fs, s->n, s->def_obj, s->fgrid, s->fshm, st));
@@ -1279,9 +1240,7 @@ static int launch_fast_path(bote_sweep* s, uint64_t rb, uint64_t re, hipStream_t
   bote::FastArgs f = s->fargs;
   f.rb = rb;
   f.re = re;
-  const uint64_t count = re - rb;
-  const uint64_t G = (uint64_t)s->fgrid * bote::FAST_BD;
-  f.runlen = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(32, count / (G * 8)));
+  f.runlen = sweep_runlen(re - rb, s->fgrid, bote::FAST_BD);
   if (s->group) {
     // cost-balanced chunks (32 per wave), taken dynamically (bote_group.hip)
     const bote_sweep::Chunks* ch = nullptr;
@@ -1321,7 +1280,7 @@ static int launch_fast_path(bote_sweep* s, uint64_t rb, uint64_t re, hipStream_t
   hipEvent_t *e0 = nullptr, *e1 = nullptr;
   int rc;
   if ((rc = timing_slot(s, e0, e1))) return rc;
-  // the kernel's events ride on its dispatch (hipExtLaunchKernelGGL): a
+  // the kernel's events ride on its dispatch (hipExtLaunchKernel): a
   // separate hipEventRecord before and after the kernel left ~10 us of idle
   // GPU each (profiles/r05b trace)
   s->last0 = *e0;
@@ -1344,8 +1303,7 @@ static int launch_fast_path(bote_sweep* s, uint64_t rb, uint64_t re, hipStream_t
   EvalArgs g = s->args;
   g.rb = rb;
   g.re = re;
-  const uint64_t GG = (uint64_t)s->grid * s->bd;
-  g.runlen = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(32, count / (GG * 8)));
+  g.runlen = sweep_runlen(re - rb, s->grid, s->bd);
   g.out_top = s->n_obj ? s->top_alt.as<Rec>() : nullptr;
   g.out_counters = s->counters_alt.as<unsigned long long>();
   g.run_if_over = s->qcount.as<unsigned long long>();
@@ -1533,10 +1491,6 @@ struct bote_search {
     DBuf local;  // the shard's result block on its own device (remote shards)
     uint64_t b = 0, e = 0;
     int dev = 0;
-    // (remote shards) peer access to the root device is enabled, so the
-    // result block's copy goes device to device over xGMI; false: the
-    // runtime stages hipMemcpyPeerAsync through host memory
-    bool peer_direct = false;
   };
   std::vector<Shard> sh;
   int root = 0;
@@ -1669,7 +1623,6 @@ int bote_search_create(const bote_planet* const* planets, uint32_t n_devices, co
         e = hipSuccess;
       }
       if (e != hipSuccess) return cleanup(hip_fail(e, "hipDeviceEnablePeerAccess (shard to root)"));
-      x.peer_direct = true;
     }
   }
   // the chunk uploads are stream-ordered before the first launch; drain them

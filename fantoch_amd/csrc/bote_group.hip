@@ -32,6 +32,7 @@
 // Reference map: see bote_kernels.hip's header (Search::compute_stats,
 // search.rs:262-319, and the Bote functions it calls, lib.rs:38-185).
 #include "bote_fast.hpp"
+#include "bote_launch.hpp"
 
 #define AS3 __attribute__((address_space(3)))
 
@@ -649,8 +650,8 @@ __global__ void __launch_bounds__(XK ? GROUP_XK_MAX_BD : GROUP_MAX_BD,
     uint32_t hq[F];  // fixed positions p_3 .. p_{N-1} (uniform)
     uint64_t base = 0;
     if (a.wstate && chunk != ~0u) {
-      // the chunk's first group, unranked on the host (bote_capi.hip
-      // sweep_chunks): the colex rank of its fixed part, then the positions
+      // the chunk's first group, unranked on the host (bote_host.cpp
+      // chunk_states): the colex rank of its fixed part, then the positions
       // as bytes (a device unrank is ~45 dependent binomial loads)
       const uint64_t* st = a.wstate + 4 * (size_t)chunk;
       base = uni64(st[0]);
@@ -1628,7 +1629,7 @@ __global__ void __launch_bounds__(XK ? GROUP_XK_MAX_BD : GROUP_MAX_BD,
                 //        S2_t = L2 + 2 sum_m D1_m q_t[m] + sum_m cnt_m q_t[m]^2
                 //      (L1 = sum of latencies = sum_m D1_m, L2 = sum of squares).
                 //      The host runs this only where the fields cannot overflow
-                //      (nc < 256, nc (16 max + 15) < 2^24; bote_capi.hip).
+                //      (nc < 256, nc (16 max + 15) < 2^24; fast_limits).
                 uint64_t L2;
                 if constexpr (BIN_FIRST) L2 = L2first;  // (the loop ran before the Q phase)
                 else if (use_lines) L2 = binned_clients(BoolC<true>{}, c0, c1, c2);
@@ -1639,7 +1640,7 @@ __global__ void __launch_bounds__(XK ? GROUP_XK_MAX_BD : GROUP_MAX_BD,
                 // (3, 4) at n = 6, PAIR2; a lone member's high half is
                 // don't-care: its table word's high half is 0), so
                 // each table's sums are one v_dot2 per word.  The host admits
-                // the bins only where nc max < 2^16 (bote_capi.hip), so every
+                // the bins only where nc max < 2^16 (bote_host.cpp), so every
                 // count, every D1_m and every cnt_m q product fits a u16.
                 constexpr int NW = NWB;
                 // the members of word i (low, high; -1: none), as in wp[t][i]
@@ -2059,21 +2060,9 @@ __global__ void __launch_bounds__(XK ? GROUP_XK_MAX_BD : GROUP_MAX_BD,
 }
 
 // ------------------------------------------------------------- launcher ---
-template <int N, bool DEF, bool SI, bool RXC, bool XK, bool BN = false>
-static hipError_t launch_group_n(const FastArgs& a, uint32_t grid, size_t shm, hipStream_t st, hipEvent_t e0,
-                                 hipEvent_t e1) {
-  auto k = sweep_group_kernel<N, DEF, SI, RXC, XK, BN>;
-  hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-  if (e != hipSuccess) return e;
-  // (timed launches carry their events in the dispatch: no marker packets
-  // before and after the kernel, which cost ~10 us of idle GPU each)
-  if (e0) hipExtLaunchKernelGGL(k, dim3(grid), dim3(a.gbd), (uint32_t)shm, st, e0, e1, 0u, a);
-  else hipLaunchKernelGGL(k, dim3(grid), dim3(a.gbd), shm, st, a);
-  return hipGetLastError();
-}
-
-// The instantiation launch_group runs for these arguments (its occupancy
-// decides the persistent grid, so it must be the kernel that runs).
+// group_fn is the one place that picks the instantiation for a set of
+// arguments: group_occupancy sizes the persistent grid from it and
+// launch_group runs it, so the grid is always that of the kernel that runs.
 // (S32 kernels also take every V in 32 bits: FastArgs::v32)
 static bool group_si(const FastArgs& a) { return a.srv_identity && a.want_digest && a.ft_metric == 2 && a.s32 && a.v32; }
 
@@ -2097,31 +2086,13 @@ static const void* group_fn_n(const FastArgs& a, bool def) {
   }
 }
 
-template <int N, bool XK>
-static hipError_t launch_group_x(const FastArgs& a, bool def, uint32_t grid, size_t shm, hipStream_t st, hipEvent_t e0,
-                                 hipEvent_t e1) {
-  if constexpr (XK) {
-    return group_si(a) ? (a.grx ? launch_group_n<N, true, true, true, true>(a, grid, shm, st, e0, e1)
-                                : launch_group_n<N, true, true, false, true>(a, grid, shm, st, e0, e1))
-                       : launch_group_n<N, true, false, false, true>(a, grid, shm, st, e0, e1);
-  } else {
-    if (def && group_si(a) && a.gbins)
-      return a.grx ? launch_group_n<N, true, true, true, false, true>(a, grid, shm, st, e0, e1)
-                   : launch_group_n<N, true, true, false, false, true>(a, grid, shm, st, e0, e1);
-    return def ? (group_si(a) ? (a.grx ? launch_group_n<N, true, true, true, false>(a, grid, shm, st, e0, e1)
-                                       : launch_group_n<N, true, true, false, false>(a, grid, shm, st, e0, e1))
-                              : launch_group_n<N, true, false, false, false>(a, grid, shm, st, e0, e1))
-               : launch_group_n<N, false, false, false, false>(a, grid, shm, st, e0, e1);
-  }
-}
-
 static const void* group_fn(const FastArgs& a, uint32_t n, bool def) {
   switch (n) {
 #define FN_CASE(NN) case NN: return a.keys ? group_fn_n<NN, true>(a, def) : group_fn_n<NN, false>(a, def);
 #define FN_CASE0(NN) case NN: return a.keys ? nullptr : group_fn_n<NN, false>(a, def);
-#ifdef BOTE_ISA_N7
+#ifdef BOTE_ISA_N7  // (analysis builds only: the n = 7 kernels, for assembly listings)
     FN_CASE(7)
-#elif defined(BOTE_ISA_N6)
+#elif defined(BOTE_ISA_N6)  // (the n = 6 kernels: BASELINE config 5)
     FN_CASE(6)
 #elif defined(BOTE_ISA_N5)
     FN_CASE(5)
@@ -2136,35 +2107,14 @@ static const void* group_fn(const FastArgs& a, uint32_t n, bool def) {
 }
 
 int group_occupancy(const FastArgs& a, uint32_t n, size_t shm, bool def) {
-  int nb = 0;
   const void* k = group_fn(a, n, def);
-  if (!k) return 0;
-  if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm) != hipSuccess) return 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, (int)a.gbd, shm) != hipSuccess) return 0;
-  return nb > 0 ? nb : 0;
+  return k ? kernel_occupancy(k, a.gbd, shm, 0) : 0;
 }
 
 hipError_t launch_group(const FastArgs& a, uint32_t n, bool def, uint32_t grid, size_t shm, hipStream_t st, hipEvent_t e0,
                         hipEvent_t e1) {
-  switch (n) {
-#define GS_CASE(NN) \
-  case NN: return a.keys ? launch_group_x<NN, true>(a, def, grid, shm, st, e0, e1) : launch_group_x<NN, false>(a, def, grid, shm, st, e0, e1);
-#define GS_CASE0(NN) \
-  case NN: return a.keys ? hipErrorInvalidValue : launch_group_x<NN, false>(a, def, grid, shm, st, e0, e1);
-#ifdef BOTE_ISA_N7  // (analysis builds only: the n = 7 kernels, for assembly listings)
-    GS_CASE(7)
-#elif defined(BOTE_ISA_N6)  // (the n = 6 kernels: BASELINE config 5)
-    GS_CASE(6)
-#elif defined(BOTE_ISA_N5)
-    GS_CASE(5)
-#else
-    GS_CASE(4) GS_CASE(5) GS_CASE(6) GS_CASE(7) GS_CASE0(8) GS_CASE0(9) GS_CASE0(10) GS_CASE0(11) GS_CASE0(12)
-    GS_CASE0(13) GS_CASE0(14) GS_CASE0(15) GS_CASE0(16)
-#endif
-#undef GS_CASE
-#undef GS_CASE0
-    default: return hipErrorInvalidValue;
-  }
+  const void* k = group_fn(a, n, def);
+  return k ? launch_kernel(k, a, grid, a.gbd, shm, st, e0, e1) : hipErrorInvalidValue;
 }
 
 }  // namespace bote

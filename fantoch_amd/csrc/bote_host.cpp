@@ -5,6 +5,8 @@
 #include <algorithm>
 #include <cmath>
 
+#include "../../include/bote_hip.h"  // (the slot and objective constants: plain C)
+
 namespace bote {
 namespace host {
 
@@ -309,6 +311,145 @@ bool fast_eligible(const uint16_t* lat, uint32_t R, const uint32_t* servers, uin
       if (i == j ? v != 0 : v == 0) return false;
     }
   return true;
+}
+
+// ------------------------------------------------------ sweep planning ---
+FastLimits fast_limits(const uint16_t* lat, uint32_t R, uint32_t nc, uint32_t n) {
+  uint32_t maxlat = 0;
+  for (size_t i = 0; i < (size_t)R * R; ++i) maxlat = std::max<uint32_t>(maxlat, lat[i]);
+  return fast_limits(maxlat, nc, n);
+}
+
+FastLimits fast_limits(uint32_t maxlat, uint32_t nc, uint32_t n) {
+  FastLimits l{};
+  l.maxlat = maxlat;
+  const uint64_t amax = 2ull * maxlat, per_quad = 4 * amax * amax;
+  l.s2_flush = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(1u << 20, per_quad ? 0xFFFFFFFFull / per_quad : 1u << 20));
+  // packed-u16 sums (group kernel): each half gains <= 2 * amax per quad
+  const uint64_t s1_flush = amax ? 0xFFFFull / (2 * amax) : 1u << 20;
+  l.g_flush = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(l.s2_flush, s1_flush));
+  // extended keys: squares of the packed keys (latency << 4 | member), two
+  // per dot2 into 32 bits (keys32 below requires 2 key^2 < 2^32)
+  const uint64_t kmax = 16ull * maxlat + 15, kq = 4 * kmax * kmax;
+  l.k_flush = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(1u << 20, 0xFFFFFFFFull / kq));
+  // every slot's sum of squares below 2^32 (a value is at most a latency
+  // plus a quorum latency, 2 max, over nc >= N clients): the bench-shaped
+  // group kernels keep the moments in 32 bits (bote_group.hip S32)
+  // (and the FPaxos moments' 24-bit multiplies: column sum + S1 <= 3 nc max < 2^24)
+  l.s32 = (uint64_t)std::max(nc, n) * amax * amax < (1ull << 32) && 3ull * nc * maxlat < (1ull << 24);
+  // and every V = cnt s2 - s1^2 in 32 bits: V = sum over pairs of
+  // (x_i - x_j)^2 <= (cnt / 2)^2 (2 max)^2 = cnt^2 max^2 for values x in
+  // [0, 2 max], so cnt max < 2^16 suffices (the kernels compute V mod 2^32
+  // from 32-bit products: exact when V < 2^32).  Round 5 asked cnt^2 (2 max)^2
+  // < 2^32, which config 5 (128 clients) missed.
+  l.v32 = l.s32 && (uint64_t)std::max(nc, n) * maxlat < (1ull << 16);
+  // the group kernel's member bins: a client count below 2^8, a sum of nc
+  // keys (latency << 4 | member) below 2^24 and two squared keys below 2^32
+  // (bote_group.hip)
+  l.bins_ok = nc < 256 && (uint64_t)nc * kmax < (1ull << 24) &&
+              (uint64_t)nc * maxlat < (1ull << 16) &&  // (packed member-pair bins)
+              2 * kmax * kmax < (1ull << 32);
+  // the group kernel's extended keys use 32-bit moments: every sum of
+  // squares nc * (2 max)^2 and 3 nc max must fit their 32/24 bits
+  l.keys32 = l.bins_ok && (uint64_t)nc * amax * amax < (1ull << 32) && 3ull * nc * maxlat < (1ull << 24);
+  return l;
+}
+
+ScoreBands score_bands(double p_fmean, double p_emean, uint32_t nc) {
+  ScoreBands b{};
+  auto integral = [](double x) { return x == (double)(int64_t)x && x > -1e12 && x < 1e12; };
+  b.p_int = integral(p_fmean) && integral(p_emean) ? 1 : 0;
+  b.p1i = b.p_int ? (int64_t)p_fmean * (int64_t)nc : 0;
+  b.p2i = b.p_int ? (int64_t)p_emean * (int64_t)nc : 0;
+  auto band = [&](double p, int64_t pi, int32_t& lo, int32_t& hi) {
+    const double t = p * (double)nc;
+    const double l = b.p_int ? (double)pi : std::floor(t) - 1.0, h = b.p_int ? (double)pi : std::ceil(t) + 1.0;
+    const double cap = 2147483647.0;  // D = a difference of two sums below 2^21
+    lo = (int32_t)std::max(-cap, std::min(cap, l));
+    hi = (int32_t)std::max(-cap, std::min(cap, h));
+  };
+  band(p_fmean, b.p1i, b.m1_lo, b.m1_hi);
+  band(p_emean, b.p2i, b.m2_lo, b.m2_hi);
+  return b;
+}
+
+const uint32_t COMPILED_OBJECTIVES[COMPILED_OBJECTIVES_KEYS][2] = {
+    {BOTE_OBJ_SCORE, 0},           {BOTE_OBJ_MEAN, BOTE_SLOT_AF1}, {BOTE_OBJ_MEAN, BOTE_SLOT_FF1},
+    {BOTE_OBJ_COV, BOTE_SLOT_AF1}, {BOTE_OBJ_MEAN, BOTE_SLOT_E},   {BOTE_OBJ_MEAN, BOTE_SLOT_TT1},
+    {BOTE_OBJ_MEAN, BOTE_SLOT_TW2}, {BOTE_OBJ_MEAN, BOTE_SLOT_FL1}};
+
+bool is_compiled_objective_set(const uint32_t* kinds, const uint32_t* slots, uint32_t n_obj, uint32_t keys) {
+  if (n_obj != (keys ? COMPILED_OBJECTIVES_KEYS : COMPILED_OBJECTIVES_BASE)) return false;
+  for (uint32_t o = 0; o < n_obj; ++o) {
+    const uint32_t kind = COMPILED_OBJECTIVES[o][0];
+    if (kinds[o] != kind || (kind != BOTE_OBJ_SCORE && slots[o] != COMPILED_OBJECTIVES[o][1])) return false;
+  }
+  return true;
+}
+
+bool slot_exists_n(uint32_t n, uint32_t slot, uint32_t keys) {
+  const bool f2 = n / 2 >= 2;  // bote_max_f(n) >= 2
+  if (slot < 10) {
+    const uint32_t b = slot % 5;
+    return !((b == BOTE_SLOT_AF2 || b == BOTE_SLOT_FF2) && !f2);
+  }
+  if (!keys || slot >= BOTE_NSLOTS_X) return false;
+  if (slot < 18) return (slot - 10) % 2 == 0 || f2;
+  return slot == 18 || f2;
+}
+
+bool chunk_states(const uint64_t* starts, uint32_t count, uint32_t n, uint32_t ns, std::vector<uint64_t>& out) {
+  const uint32_t F = n - 3;
+  out.assign((size_t)count * 4, 0);
+  std::vector<uint32_t> p(n);
+  for (uint32_t i = 0; i < count; ++i) {
+    if (!colex_unrank(starts[i], n, ns, p.data())) return false;
+    uint64_t base = 0, b[2] = {0, 0};
+    for (uint32_t k = 0; k < F; ++k) {
+      base += binom_u64(p[3 + k], k + 4);
+      b[k / 8] |= (uint64_t)p[3 + k] << (8 * (k % 8));
+    }
+    out[4 * (size_t)i] = base;
+    out[4 * (size_t)i + 1] = b[0];
+    out[4 * (size_t)i + 2] = b[1];
+  }
+  return true;
+}
+
+// sample steps per wave on a full range (r03v A/B: 8 vs 1, kernel -1.6 %, 1/8
+// shard -5 %; r05g: 4 and 8 give the same R=64 n=7 step, 14.15-14.17 vs
+// 14.16-14.25 ms, and 4 halves the sample launch: 0.14 vs 0.18 ms outside the kernel)
+constexpr uint32_t SEED_STEPS = 4;
+uint32_t sample_count(uint64_t rb, uint64_t re, uint64_t total, uint32_t nwaves, uint32_t K) {
+  const uint32_t base = std::min<uint32_t>(4096, nwaves);
+  // SEED_STEPS one-step chunks per wave, disjoint and at most 1/8 of the
+  // range.  (Chunks of 8 consecutive steps, 4,096 of them, measured slower:
+  // kernel 15.52 vs 15.35 ms, their K least minima are a looser bound, r03x.)
+  const uint64_t fit = (re - rb) / (64 * 8);
+  // sample steps per wave: SEED_STEPS on a full sweep; a shard's launch
+  // scales them by sqrt(its share of the rank space), rounded up: the sample
+  // costs ~ steps, the block merges it saves
+  // ~ range / steps, so the best count grows as sqrt(range).  r05g, R=64 n=7
+  // shards, 8 scaled (8 / 3 / 1 steps) against 8 fixed: 1/8 shard 2.089 vs
+  // 2.125 ms per step, 1/64 0.492 vs 0.531 ms
+  const double share = (double)(re - rb) / (double)total;
+  const uint32_t steps =
+      (uint32_t)std::max(1.0, std::min((double)SEED_STEPS, std::ceil(SEED_STEPS * std::sqrt(share) - 1e-9)));
+  const uint32_t nsamp =
+      (uint32_t)std::min<uint64_t>({(uint64_t)base * std::max<uint32_t>(1, steps), std::max<uint64_t>(base, fit), 65536});
+  if (nsamp < K || re - rb < (uint64_t)nsamp * 64 * 8) return 0;
+  return nsamp;
+}
+
+std::vector<uint64_t> sample_starts(uint64_t rb, uint64_t re, uint32_t nsamp) {
+  std::vector<uint64_t> s(nsamp);
+  for (uint32_t i = 0; i < nsamp; ++i) s[i] = rb + (uint64_t)(((unsigned __int128)(re - rb - 64) * i) / nsamp);
+  return s;
+}
+
+uint32_t sweep_runlen(uint64_t count, uint32_t grid, uint32_t bd) {
+  const uint64_t G = (uint64_t)grid * bd;
+  return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(32, count / (G * 8)));
 }
 
 void unpack_result(const uint8_t* blk, uint32_t n_obj, uint32_t K, uint32_t kp, TopkRecord* out, uint32_t* out_count,

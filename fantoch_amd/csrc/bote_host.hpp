@@ -1,7 +1,10 @@
 // bote_host.hpp — host-only pieces of libbote_hip.so (plain C++, no HIP): the
 // combinatorics of colex ranks, the group walk behind the cost-balanced work
 // chunks and shard splits, the client-quad layouts, the fast-path eligibility
-// test and the result-block unpacking.  Compiled by g++ into the library and,
+// test, the sweep planning (the exactness limits and flush counts of the fast
+// kernels, the score bands, the compiled-in objective set, the chunk states
+// and the top-K seed's sample plan) and the result-block unpacking.  Compiled
+// by g++ into the library and,
 // separately, under ASan/UBSan by tests/test_sanitize.py (tests/native/
 // host_check.cpp), so the driver's host code runs under the sanitizers the
 // oracle does.
@@ -88,6 +91,65 @@ std::vector<uint32_t> low_table(uint32_t m);
 // the servers, >= 2 clients, and no fairness threshold.
 bool fast_eligible(const uint16_t* lat, uint32_t R, const uint32_t* servers, uint32_t ns, uint32_t nc,
                    bool fairness_threshold);
+
+// ------------------------------------------------------ sweep planning ---
+// The integer arithmetic of bote_sweep_create_keys (bote_capi.hip): which
+// kernel variants are exact for a planet and client count, and how often
+// their narrow accumulators flush.  The C ABI copies these into FastArgs.
+struct FastLimits {
+  uint32_t maxlat;    // the largest latency of the planet
+  uint32_t s2_flush;  // FastArgs::s2_flush, g_flush, k_flush (never 0)
+  uint32_t g_flush;
+  uint32_t k_flush;
+  bool s32;      // FastArgs::s32: every slot's moments fit 32 bits
+  bool v32;      // FastArgs::v32: s32, and every V = cnt s2 - s1^2 fits 32 bits
+  bool bins_ok;  // the member bins of the group kernel cannot overflow
+  bool keys32;   // bins_ok, and the extended keys' 32-bit moments are exact
+};
+FastLimits fast_limits(uint32_t maxlat, uint32_t nc, uint32_t n);
+// (maxlat: the maximum over the R x R matrix)
+FastLimits fast_limits(const uint16_t* lat, uint32_t R, uint32_t nc, uint32_t n);
+
+// The group kernel's mean tests of compute_score (FastArgs::p_int .. m2_hi):
+// p_int when both thresholds are integers, then p1i / p2i = threshold * nc;
+// [lo, hi] is the band of the integer difference D in which the kernel falls
+// back to the reference's f64 arithmetic (lo = hi = p * nc when p_int, else
+// floor(p * nc) - 1 and ceil(p * nc) + 1), clamped to +-(2^31 - 1).
+struct ScoreBands {
+  int p_int;
+  int64_t p1i, p2i;
+  int32_t m1_lo, m1_hi, m2_lo, m2_hi;
+};
+ScoreBands score_bands(double p_fmean, double p_emean, uint32_t nc);
+
+// The objective set compiled into the group kernel (DEF kernels), as
+// (kind, slot) pairs: bote.py CONFIG5_OBJECTIVES, whose first
+// COMPILED_OBJECTIVES_BASE entries are DEFAULT_OBJECTIVES (SCORE, MEAN af1,
+// MEAN ff1, COV af1, MEAN e; then MEAN tt1, MEAN tw2, MEAN fl1).
+constexpr uint32_t COMPILED_OBJECTIVES_BASE = 5, COMPILED_OBJECTIVES_KEYS = 8;
+extern const uint32_t COMPILED_OBJECTIVES[COMPILED_OBJECTIVES_KEYS][2];
+// True when the n_obj objectives are exactly that set: the first five on the
+// base key set (keys == 0), all eight on the extended one.  A SCORE
+// objective's slot is not compared.
+bool is_compiled_objective_set(const uint32_t* kinds, const uint32_t* slots, uint32_t n_obj, uint32_t keys);
+// Slot `slot` exists for config size n (f = 2 keys need max_f >= 2); slots
+// >= 10 only with the extended key set.
+bool slot_exists_n(uint32_t n, uint32_t slot, uint32_t keys);
+
+// Per start rank, the 4 u64 of FastArgs::wstate: the colex rank of the
+// config's n - 3 largest positions (its group: the config with its three
+// lowest positions zeroed), then those positions as bytes in two words (n - 3
+// <= 16), then 0.  False when a rank is out of range.
+bool chunk_states(const uint64_t* starts, uint32_t count, uint32_t n, uint32_t ns, std::vector<uint64_t>& out);
+// The sample launch of the top-K seed over [rb, re) of `total` ranks, on
+// nwaves waves, for the K least: the number of one-step (64-config) sample
+// chunks, 0 when the range is too small to sample.
+uint32_t sample_count(uint64_t rb, uint64_t re, uint64_t total, uint32_t nwaves, uint32_t K);
+// Their start ranks: evenly spaced over [rb, re - 64].
+std::vector<uint64_t> sample_starts(uint64_t rb, uint64_t re, uint32_t nsamp);
+// Consecutive ranks per lane job of the fast and generic kernels: 1 to 32, so
+// that a launch of `count` ranks has ~8 jobs per lane on grid x bd lanes.
+uint32_t sweep_runlen(uint64_t count, uint32_t grid, uint32_t bd);
 
 // -------------------------------------------------------- result blocks --
 // A result block is [n_obj x kp records {key, rank} (16 B), ascending, padded

@@ -19,6 +19,7 @@
 //   k_single_*             Bote::{leaderless, leader, all_leaders_stats, best_leader}
 #include <atomic>
 #include "bote_kernels.hpp"
+#include "bote_launch.hpp"
 
 namespace bote {
 
@@ -705,15 +706,6 @@ __global__ void __launch_bounds__(256) best_leader_kernel(SingleArgs a, const ui
 }
 
 // ------------------------------------------------------------- launchers --
-template <int N, bool FULL, bool X>
-static hipError_t launch_eval_n(const EvalArgs& a, uint32_t grid, uint32_t bd, size_t shm, hipStream_t st) {
-  auto k = eval_kernel<N, FULL, X>;
-  hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k, dim3(grid), dim3(bd), shm, st, a);
-  return hipGetLastError();
-}
-
 size_t eval_smem_bytes(const EvalArgs& a, uint32_t n, uint32_t bd, bool topk) {
   size_t off[11];
   int nl = 0;
@@ -728,39 +720,30 @@ size_t eval_smem_bytes(const EvalArgs& a, uint32_t n, uint32_t bd, bool topk) {
   return smem_layout(a, (int)n, (nl + 1) / 2, bd, topk, off);
 }
 
-int eval_occupancy(uint32_t n, bool full, uint32_t bd, size_t shm, bool x) {
-  int nb = 0;
-  const void* k = nullptr;
+// the kernel for config size n, full outputs or top-K, base or extended keys
+// (null: unsupported n), for the occupancy query and the launch alike
+static const void* eval_fn(uint32_t n, bool full, bool keys) {
   switch (n) {
-#define OCC_CASE(NN)                                                                                       \
-  case NN:                                                                                                 \
-    k = x ? (full ? (const void*)eval_kernel<NN, true, true> : (const void*)eval_kernel<NN, false, true>)  \
-          : (full ? (const void*)eval_kernel<NN, true, false> : (const void*)eval_kernel<NN, false, false>); \
-    break;
-    OCC_CASE(2) OCC_CASE(3) OCC_CASE(4) OCC_CASE(5) OCC_CASE(6) OCC_CASE(7) OCC_CASE(8) OCC_CASE(9)
-    OCC_CASE(10) OCC_CASE(11) OCC_CASE(12) OCC_CASE(13) OCC_CASE(14) OCC_CASE(15) OCC_CASE(16)
-#undef OCC_CASE
-    default: return 0;
+#define FN_CASE(NN)                                                                                             \
+  case NN:                                                                                                      \
+    return keys ? (full ? (const void*)eval_kernel<NN, true, true> : (const void*)eval_kernel<NN, false, true>) \
+                : (full ? (const void*)eval_kernel<NN, true, false> : (const void*)eval_kernel<NN, false, false>);
+    FN_CASE(2) FN_CASE(3) FN_CASE(4) FN_CASE(5) FN_CASE(6) FN_CASE(7) FN_CASE(8) FN_CASE(9)
+    FN_CASE(10) FN_CASE(11) FN_CASE(12) FN_CASE(13) FN_CASE(14) FN_CASE(15) FN_CASE(16)
+#undef FN_CASE
+    default: return nullptr;
   }
-  if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm) != hipSuccess) return 1;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, (int)bd, shm) != hipSuccess) return 1;
-  return nb > 0 ? nb : 1;
+}
+
+int eval_occupancy(uint32_t n, bool full, uint32_t bd, size_t shm, bool keys) {
+  const void* k = eval_fn(n, full, keys);
+  return k ? kernel_occupancy(k, bd, shm, 1) : 0;
 }
 
 hipError_t launch_eval(const EvalArgs& a, uint32_t n, bool full, uint32_t grid, uint32_t bd, size_t shm,
                        hipStream_t st) {
-  switch (n) {
-#define EV_CASE(NN)                                                                                 \
-  case NN:                                                                                          \
-    return a.keys ? (full ? launch_eval_n<NN, true, true>(a, grid, bd, shm, st)                     \
-                          : launch_eval_n<NN, false, true>(a, grid, bd, shm, st))                   \
-                  : (full ? launch_eval_n<NN, true, false>(a, grid, bd, shm, st)                    \
-                          : launch_eval_n<NN, false, false>(a, grid, bd, shm, st));
-    EV_CASE(2) EV_CASE(3) EV_CASE(4) EV_CASE(5) EV_CASE(6) EV_CASE(7) EV_CASE(8) EV_CASE(9)
-    EV_CASE(10) EV_CASE(11) EV_CASE(12) EV_CASE(13) EV_CASE(14) EV_CASE(15) EV_CASE(16)
-#undef EV_CASE
-    default: return hipErrorInvalidValue;
-  }
+  const void* k = eval_fn(n, full, a.keys != 0);
+  return k ? launch_kernel(k, a, grid, bd, shm, st) : hipErrorInvalidValue;
 }
 
 hipError_t launch_merge(const Rec* src, uint32_t n_lists, uint64_t list_stride, Rec* dst, uint64_t out_stride,

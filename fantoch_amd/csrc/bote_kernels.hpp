@@ -210,7 +210,7 @@ struct FastArgs {
 #endif
 size_t fast_smem_bytes(const FastArgs& a, uint32_t n);
 int fast_occupancy(uint32_t n, size_t shm);
-// (e0, e1: events carried by the dispatch itself, hipExtLaunchKernelGGL, for a timed launch)
+// (e0, e1: events carried by the dispatch itself, bote_launch.hpp, for a timed launch)
 hipError_t launch_fast(const FastArgs& a, uint32_t n, uint32_t grid, size_t shm, hipStream_t st, hipEvent_t e0 = nullptr,
                        hipEvent_t e1 = nullptr);
 size_t group_smem_bytes(const FastArgs& a, uint32_t n);

@@ -24,6 +24,7 @@
 // Input leaderless keys by the packed client-quad loop; compute_score validity
 // by integer / f64-margin decisions; digest; block top-K.
 #include "bote_fast.hpp"
+#include "bote_launch.hpp"
 
 
 namespace bote {
@@ -457,41 +458,27 @@ __global__ void __launch_bounds__(FAST_BD, 4) sweep_fast_kernel(FastArgs a) {
 }
 
 // ------------------------------------------------------------- launcher ---
-template <int N>
-static hipError_t launch_fast_n(const FastArgs& a, uint32_t grid, size_t shm, hipStream_t st, hipEvent_t e0,
-                                hipEvent_t e1) {
-  auto k = sweep_fast_kernel<N>;
-  hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-  if (e != hipSuccess) return e;
-  if (e0) hipExtLaunchKernelGGL(k, dim3(grid), dim3(FAST_BD), (uint32_t)shm, st, e0, e1, 0u, a);
-  else hipLaunchKernelGGL(k, dim3(grid), dim3(FAST_BD), shm, st, a);
-  return hipGetLastError();
+// the kernel for config size n (null: unsupported), for the occupancy query
+// and the launch alike
+static const void* fast_fn(uint32_t n) {
+  switch (n) {
+#define FN_CASE(NN) case NN: return (const void*)sweep_fast_kernel<NN>;
+    FN_CASE(2) FN_CASE(3) FN_CASE(4) FN_CASE(5) FN_CASE(6) FN_CASE(7) FN_CASE(8) FN_CASE(9)
+    FN_CASE(10) FN_CASE(11) FN_CASE(12) FN_CASE(13) FN_CASE(14) FN_CASE(15) FN_CASE(16)
+#undef FN_CASE
+    default: return nullptr;
+  }
 }
 
 int fast_occupancy(uint32_t n, size_t shm) {
-  int nb = 0;
-  const void* k = nullptr;
-  switch (n) {
-#define OCC_CASE(NN) case NN: k = (const void*)sweep_fast_kernel<NN>; break;
-    OCC_CASE(2) OCC_CASE(3) OCC_CASE(4) OCC_CASE(5) OCC_CASE(6) OCC_CASE(7) OCC_CASE(8) OCC_CASE(9)
-    OCC_CASE(10) OCC_CASE(11) OCC_CASE(12) OCC_CASE(13) OCC_CASE(14) OCC_CASE(15) OCC_CASE(16)
-#undef OCC_CASE
-    default: return 0;
-  }
-  if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm) != hipSuccess) return 1;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, (int)FAST_BD, shm) != hipSuccess) return 1;
-  return nb > 0 ? nb : 1;
+  const void* k = fast_fn(n);
+  return k ? kernel_occupancy(k, FAST_BD, shm, 1) : 0;
 }
 
 hipError_t launch_fast(const FastArgs& a, uint32_t n, uint32_t grid, size_t shm, hipStream_t st, hipEvent_t e0,
                        hipEvent_t e1) {
-  switch (n) {
-#define FS_CASE(NN) case NN: return launch_fast_n<NN>(a, grid, shm, st, e0, e1);
-    FS_CASE(2) FS_CASE(3) FS_CASE(4) FS_CASE(5) FS_CASE(6) FS_CASE(7) FS_CASE(8) FS_CASE(9)
-    FS_CASE(10) FS_CASE(11) FS_CASE(12) FS_CASE(13) FS_CASE(14) FS_CASE(15) FS_CASE(16)
-#undef FS_CASE
-    default: return hipErrorInvalidValue;
-  }
+  const void* k = fast_fn(n);
+  return k ? launch_kernel(k, a, grid, FAST_BD, shm, st, e0, e1) : hipErrorInvalidValue;
 }
 
 }  // namespace bote

@@ -1,11 +1,14 @@
 // Host-code checker for libbote_hip.so's host-only translation unit
 // (fantoch_amd/csrc/bote_host.cpp), built with ASan + UBSan by
 // tests/test_sanitize.py: colex ranks, the binomial table, the group walk and
-// its chunk/shard cuts, quad layouts, the low table, fast-path eligibility and
+// its chunk/shard cuts, quad layouts, the low table, fast-path eligibility,
+// the sweep planning (fast_limits, score_bands, the compiled-in objective set,
+// slot_exists_n, chunk_states, the seed's sample plan, sweep_runlen) and
 // result-block unpacking, each against a direct restatement.  Prints
 // "host ok" on success; any failed check exits 1.
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -273,7 +276,264 @@ static void check_chunks_per_wave() {
   CHECK(chunks_per_wave(1ull << 40, 4096, 64, 2) == 2);
 }
 
+// ------------------------------------------------------ sweep planning ---
+// The arithmetic of bote_sweep_create_keys as it stood in the C ABI before it
+// moved to bote_host.cpp, restated inequality by inequality.
+struct LimitsRef {
+  bool s32, v32, bins, keys32;
+};
+static LimitsRef limits_ref(uint64_t maxlat, uint32_t nc, uint32_t n) {
+  const uint64_t two32 = 1ull << 32, two24 = 1ull << 24, two16 = 1ull << 16;
+  const uint64_t cnt = nc > n ? nc : n, a = 2 * maxlat, key = 16 * maxlat + 15;
+  LimitsRef r;
+  r.s32 = cnt * a * a < two32 && 3ull * nc * maxlat < two24;
+  r.v32 = r.s32 && cnt * maxlat < two16;
+  r.bins = nc < 256 && (uint64_t)nc * key < two24 && (uint64_t)nc * maxlat < two16 && 2 * key * key < two32;
+  r.keys32 = (uint64_t)nc * a * a < two32 && (uint64_t)nc * maxlat < two16 && 3ull * nc * maxlat < two24 && nc < 256 &&
+             (uint64_t)nc * key < two24 && 2 * key * key < two32;
+  return r;
+}
+
+static void check_fast_limits() {
+  // the shipped shapes, nc = R.  Maximum latencies read off the planets:
+  // fantoch_amd.planet.Planet.synthetic(64).lat.max() = 350,
+  // Planet.synthetic(128).lat.max() = 351, Planet.new().lat.max() = 381 (GCP)
+  {
+    std::vector<uint16_t> lat(64 * 64, 5);
+    lat[17 * 64 + 3] = 350;  // (the maximum is taken over the whole matrix)
+    const FastLimits l = fast_limits(lat.data(), 64, 64, 7);
+    CHECK(l.maxlat == 350 && l.s32 && l.v32 && l.bins_ok && l.keys32);
+    const FastLimits m = fast_limits(350, 64, 7);
+    CHECK(m.s2_flush == l.s2_flush && m.g_flush == l.g_flush && m.k_flush == l.k_flush);
+  }
+  {
+    const FastLimits l = fast_limits(351, 128, 6);
+    CHECK(l.s32 && l.v32 && l.bins_ok && l.keys32);
+  }
+  for (uint32_t n : {3u, 5u, 7u, 13u}) {
+    const FastLimits l = fast_limits(381, 20, n);
+    CHECK(l.s32 && l.v32);
+  }
+  // v32: max(nc, n) * maxlat = 2^16 - 1 against 2^16, through nc and through n
+  CHECK(fast_limits(257, 255, 7).v32 && 255 * 257 == 65535);
+  CHECK(!fast_limits(256, 256, 7).v32 && fast_limits(256, 256, 7).s32);
+  CHECK(fast_limits(4095, 2, 16).v32 && !fast_limits(4096, 2, 16).v32 && fast_limits(4096, 2, 16).s32);
+  // a doubled R=128 planet with 128 clients: 32-bit moments, 64-bit V
+  CHECK(fast_limits(600, 128, 6).s32 && !fast_limits(600, 128, 6).v32);
+  CHECK(fast_limits(702, 128, 7).s32 && !fast_limits(702, 128, 7).v32);  // 2 * Planet.synthetic(128)
+  // s32 at 2^32: max(nc, n) (2 max)^2 = 2^32 at 1024 clients of latency 1024
+  CHECK(fast_limits(1024, 1023, 7).s32 && !fast_limits(1024, 1024, 7).s32);
+  CHECK(fast_limits(8191, 2, 16).s32 && !fast_limits(8192, 2, 16).s32);  // (n counts: 16 * 16384^2 = 2^32)
+  // s32 at 2^24: 3 nc max = 2^24 - 1 (3 * 53261 * 105) against one client more
+  CHECK(3ull * 53261 * 105 == (1ull << 24) - 1);
+  CHECK(fast_limits(105, 53261, 7).s32 && !fast_limits(105, 53262, 7).s32);
+  // bins_ok: the client count, the packed member-pair sums (nc max < 2^16)
+  // and two squared keys (2 (16 max + 15)^2 < 2^32: max <= 2895)
+  CHECK(fast_limits(200, 255, 7).bins_ok && !fast_limits(200, 256, 7).bins_ok);
+  CHECK(fast_limits(257, 255, 7).bins_ok && !fast_limits(258, 255, 7).bins_ok);
+  CHECK(fast_limits(2895, 20, 7).bins_ok && !fast_limits(2896, 20, 7).bins_ok);
+  CHECK(fast_limits(2895, 20, 7).keys32 && !fast_limits(2896, 20, 7).keys32);
+  CHECK(fast_limits(200, 255, 7).keys32 && !fast_limits(200, 256, 7).keys32);
+  // keys32's other 2^32 and 2^24 terms (nc (2 max)^2, 3 nc max, nc (16 max +
+  // 15)) cannot bind once nc max < 2^16 and max <= 2895 hold, so no input sits
+  // on their edges; every term is compared with the restatement instead, on a
+  // grid that holds each boundary value and its neighbours
+  const uint32_t lats[] = {0, 1, 2, 105, 255, 256, 257, 258, 350, 351, 381, 511, 512, 600, 702, 1023, 1024, 1025,
+                           2047, 2048, 2895, 2896, 4095, 4096, 8191, 8192, 16383, 65535};
+  const uint32_t ncs[] = {0, 1, 2, 16, 17, 20, 22, 23, 63, 64, 127, 128, 254, 255, 256, 257, 1023, 1024, 4096, 53261,
+                          53262};
+  for (uint32_t m : lats)
+    for (uint32_t nc : ncs)
+      for (uint32_t n : {2u, 7u, 16u}) {
+        const FastLimits l = fast_limits(m, nc, n);
+        const LimitsRef r = limits_ref(m, nc, n);
+        CHECK(l.s32 == r.s32 && l.v32 == r.v32 && l.bins_ok == r.bins && l.keys32 == r.keys32);
+        CHECK(!l.keys32 || l.bins_ok);
+      }
+  // flush counts: never 0, and count x the most one quad adds stays inside
+  // the accumulator: 4 (2 max)^2 per quad into 32 bits, 2 (2 max) per quad into
+  // a packed 16-bit half, 4 (16 max + 15)^2 per quad into 32 bits
+  for (uint32_t m : {0u, 1u, 350u, 351u, 381u, 4095u}) {
+    const FastLimits l = fast_limits(m, 64, 7);
+    const uint64_t amax = 2ull * m, per_quad = 4 * amax * amax, key = 16ull * m + 15, kq = 4 * key * key;
+    CHECK(l.s2_flush >= 1 && l.g_flush >= 1 && l.k_flush >= 1);
+    CHECK(l.s2_flush <= (1u << 20) && l.g_flush <= l.s2_flush && l.k_flush <= (1u << 20));
+    CHECK((uint64_t)l.s2_flush * per_quad < (1ull << 32));
+    CHECK((uint64_t)l.g_flush * per_quad < (1ull << 32));
+    CHECK((uint64_t)l.g_flush * 2 * amax < (1ull << 16));
+    // (one quad of squared keys passes 2^32 from max = 2048 on, where no
+    // flush count can help: k_flush is 1 there.  At 4095 the extended keys do
+    // not run on the group kernel at all: keys32 is false.)
+    if (kq < (1ull << 32)) CHECK((uint64_t)l.k_flush * kq < (1ull << 32));
+    else CHECK(l.k_flush == 1);
+    if (m == 4095) CHECK(!l.keys32 && !l.bins_ok);
+  }
+  CHECK(fast_limits(0, 64, 7).s2_flush == (1u << 20) && fast_limits(0, 64, 7).g_flush == (1u << 20));
+  CHECK(fast_limits(4095, 64, 7).s2_flush == 16 && fast_limits(4095, 64, 7).g_flush == 4);
+}
+
+static void check_score_bands() {
+  // bote.py DEFAULT_RANKING: min_mean_fpaxos_improv 110, min_mean_epaxos_improv 35
+  for (uint32_t nc : {20u, 64u, 128u}) {
+    const ScoreBands b = score_bands(110.0, 35.0, nc);
+    CHECK(b.p_int == 1 && b.p1i == 110 * (int64_t)nc && b.p2i == 35 * (int64_t)nc);
+    CHECK(b.m1_lo == b.p1i && b.m1_hi == b.p1i && b.m2_lo == b.p2i && b.m2_hi == b.p2i);
+  }
+  {
+    const ScoreBands b = score_bands(-3.0, 0.0, 7);
+    CHECK(b.p_int == 1 && b.p1i == -21 && b.p2i == 0 && b.m1_lo == -21 && b.m1_hi == -21 && b.m2_lo == 0);
+  }
+  // one threshold not an integer: both tests fall back to bands around p * nc
+  const double ps[][2] = {{110.5, 35.0}, {110.0, 35.25}, {0.1, -0.1}, {-17.75, 1e-9}, {1234.5678, -999.001}};
+  for (auto& p : ps)
+    for (uint32_t nc : {1u, 3u, 20u, 64u, 127u, 4096u}) {
+      const ScoreBands b = score_bands(p[0], p[1], nc);
+      CHECK(b.p_int == 0 && b.p1i == 0 && b.p2i == 0);
+      CHECK((double)b.m1_lo <= std::floor(p[0] * nc) - 1 && (double)b.m1_hi >= std::ceil(p[0] * nc) + 1);
+      CHECK((double)b.m2_lo <= std::floor(p[1] * nc) - 1 && (double)b.m2_hi >= std::ceil(p[1] * nc) + 1);
+      CHECK(b.m1_lo < b.m1_hi && b.m2_lo < b.m2_hi);
+    }
+  // bands clamp at +-(2^31 - 1), integral or not
+  const int32_t cap = 2147483647;
+  {
+    const ScoreBands b = score_bands(1e9, -1e9, 64);
+    CHECK(b.p_int == 1 && b.p1i == 64000000000ll && b.p2i == -64000000000ll);
+    CHECK(b.m1_lo == cap && b.m1_hi == cap && b.m2_lo == -cap && b.m2_hi == -cap);
+  }
+  {
+    const ScoreBands b = score_bands(1e9 + 0.5, -1e9 - 0.5, 64);
+    CHECK(b.p_int == 0 && b.m1_lo == cap && b.m1_hi == cap && b.m2_lo == -cap && b.m2_hi == -cap);
+  }
+  {
+    const ScoreBands b = score_bands(1e13, 35.0, 2);  // past the integral range: treated as non-integral
+    CHECK(b.p_int == 0 && b.m1_hi == cap && b.m2_lo == 69 && b.m2_hi == 71);
+  }
+}
+
+static void check_objective_sets() {
+  // fantoch_amd/bote.py DEFAULT_OBJECTIVES and CONFIG5_OBJECTIVES as (kind, slot)
+  const uint32_t def[5][2] = {{0, 0}, {1, 0}, {1, 1}, {2, 0}, {1, 4}};
+  const uint32_t c5[8][2] = {{0, 0}, {1, 0}, {1, 1}, {2, 0}, {1, 4}, {1, 10}, {1, 13}, {1, 18}};
+  auto match = [](const uint32_t (*o)[2], uint32_t n_obj, uint32_t keys) {
+    std::vector<uint32_t> k(n_obj), s(n_obj);
+    for (uint32_t i = 0; i < n_obj; ++i) {
+      k[i] = o[i][0];
+      s[i] = o[i][1];
+    }
+    return is_compiled_objective_set(k.data(), s.data(), n_obj, keys);
+  };
+  CHECK(match(def, 5, 0));
+  CHECK(match(c5, 8, 1));
+  CHECK(!match(def, 5, 1));  // the base set with the extended keys
+  CHECK(!match(c5, 8, 0));   // (and the other way round)
+  CHECK(!match(c5, 5, 1) && !match(def, 4, 0) && !match(c5, 7, 1) && !match(c5, 6, 0) && !match(def, 0, 0));
+  for (uint32_t keys = 0; keys < 2; ++keys) {
+    const uint32_t n_obj = keys ? 8 : 5;
+    for (uint32_t i = 0; i < n_obj; ++i) {
+      uint32_t o[8][2];
+      std::memcpy(o, c5, sizeof(o));
+      o[i][0] = (o[i][0] + 1) % 3;  // one kind changed
+      CHECK(!match(o, n_obj, keys));
+      std::memcpy(o, c5, sizeof(o));
+      o[i][1] += 1;  // one slot changed: refused, but for SCORE, whose slot is not read
+      CHECK(match(o, n_obj, keys) == (i == 0));
+    }
+  }
+  for (uint32_t i = 0; i < COMPILED_OBJECTIVES_KEYS; ++i)
+    CHECK(COMPILED_OBJECTIVES[i][0] == c5[i][0] && COMPILED_OBJECTIVES[i][1] == c5[i][1]);
+  // slots: f = 2 keys (af2, ff2: 2, 3, 7, 8) need n >= 4; slots 10..19 the extended set
+  for (uint32_t n = 2; n <= 16; ++n)
+    for (uint32_t slot = 0; slot < 24; ++slot)
+      for (uint32_t keys = 0; keys < 2; ++keys) {
+        const bool f2 = n >= 4;
+        bool want;
+        if (slot < 10) want = !(slot % 5 == 2 || slot % 5 == 3) || f2;
+        else if (!keys || slot >= 20) want = false;
+        else if (slot < 18) want = slot % 2 == 0 || f2;  // tt1, tt2, tw1, tw2 and their colocated four
+        else want = slot == 18 || f2;                    // fl1, fl2
+        CHECK(slot_exists_n(n, slot, keys) == want);
+      }
+}
+
+static void check_chunk_states() {
+  std::mt19937_64 rng(23);
+  const uint32_t shapes[][2] = {{4, 20}, {7, 64}, {16, 20}};
+  for (auto& sh : shapes) {
+    const uint32_t n = sh[0], ns = sh[1];
+    const uint64_t total = binom_u64(ns, n);
+    std::vector<uint64_t> starts = {0, total - 1};
+    for (int i = 0; i < 500; ++i) starts.push_back(rng() % total);
+    std::vector<uint64_t> st;
+    CHECK(chunk_states(starts.data(), (uint32_t)starts.size(), n, ns, st));
+    CHECK(st.size() == starts.size() * 4);
+    std::vector<uint32_t> p(n);
+    for (size_t i = 0; i < starts.size(); ++i) {
+      CHECK(colex_unrank(starts[i], n, ns, p.data()));
+      // word 0: the rank with the three lowest positions' terms zeroed, which
+      // is the colex rank of the group's first config (0, 1, 2, p3, ...)
+      std::vector<uint32_t> g(p);
+      g[0] = 0;
+      g[1] = 1;
+      g[2] = 2;
+      CHECK(st[4 * i] == colex_rank(g.data(), n));
+      CHECK(st[4 * i] <= starts[i] && starts[i] - st[4 * i] < binom_u64(p[3], 3));
+      // words 1, 2: the n - 3 largest positions, one byte each
+      for (uint32_t k = 0; k + 3 < n; ++k) CHECK(((st[4 * i + 1 + k / 8] >> (8 * (k % 8))) & 0xFF) == p[3 + k]);
+      for (uint32_t k = n - 3; k < 16; ++k) CHECK(((st[4 * i + 1 + k / 8] >> (8 * (k % 8))) & 0xFF) == 0);
+      CHECK(st[4 * i + 3] == 0);
+    }
+    starts.push_back(total);  // out of range
+    CHECK(!chunk_states(starts.data(), (uint32_t)starts.size(), n, ns, st));
+  }
+  std::vector<uint64_t> st = {1, 2, 3};
+  CHECK(chunk_states(nullptr, 0, 7, 64, st) && st.empty());
+}
+
+static void check_sample_plan() {
+  const uint64_t total = binom_u64(64, 7);
+  // a full R=64 n=7 launch on 4,096 waves: 4 one-step chunks per wave
+  CHECK(sample_count(0, total, total, 4096, 100) == 16384);
+  CHECK(sample_count(0, total, total, 1024, 100) == 4096);
+  // shards: steps per wave scale with sqrt(share), rounded up: 1/8 -> 2, 1/64 -> 1
+  CHECK(sample_count(0, total / 8, total, 4096, 100) == 8192);
+  CHECK(sample_count(total / 2, total / 2 + total / 64, total, 4096, 100) == 4096);
+  // at most 4,096 waves' worth of chunks; fewer chunks than K: no seed
+  CHECK(sample_count(0, 1ull << 40, 1ull << 40, 1u << 20, 100) == 16384);
+  CHECK(sample_count(0, total, total, 16, 100) == 0);
+  CHECK(sample_count(0, total, total, 0, 1) == 0);
+  // too small to sample: the chunks (64 configs each) may cover at most 1/8 of the range
+  CHECK(sample_count(1000, 1000 + 4096ull * 512, total, 4096, 100) == 4096);
+  CHECK(sample_count(1000, 1000 + 4096ull * 512 - 1, total, 4096, 100) == 0);
+  CHECK(sample_count(0, 0, total, 4096, 100) == 0 && sample_count(0, 63, total, 4096, 1) == 0);
+  std::mt19937_64 rng(31);
+  for (int i = 0; i < 2000; ++i) {
+    const uint64_t tot = i % 2 ? total : binom_u64(128, 6);
+    const uint64_t rb = rng() % tot, len = i % 3 ? rng() % (tot - rb + 1) : rng() % std::min<uint64_t>(tot - rb + 1, 1 << 22);
+    const uint32_t nwaves = 1 + (uint32_t)(rng() % 8192), K = 1 + (uint32_t)(rng() % 128);
+    const uint32_t ns = sample_count(rb, rb + len, tot, nwaves, K);
+    if (!ns) continue;
+    CHECK(ns >= K && ns <= 65536 && len >= (uint64_t)ns * 512);
+    const auto s = sample_starts(rb, rb + len, ns);
+    CHECK(s.size() == ns && s.front() == rb && s.back() <= rb + len - 64);
+    for (size_t j = 1; j < s.size(); ++j) CHECK(s[j] >= s[j - 1] + 64);
+  }
+  // runs of consecutive ranks per lane job: ~8 jobs per lane, 1 to 32
+  CHECK(sweep_runlen(0, 1024, 256) == 1 && sweep_runlen(1024ull * 256 * 8 * 2 - 1, 1024, 256) == 1);
+  CHECK(sweep_runlen(1024ull * 256 * 8 * 2, 1024, 256) == 2);
+  CHECK(sweep_runlen(1024ull * 256 * 8 * 32, 1024, 256) == 32 && sweep_runlen(1ull << 62, 1024, 256) == 32);
+  for (int i = 0; i < 200; ++i) {
+    const uint64_t count = rng() >> (rng() % 50);
+    const uint32_t grid = 1 + (uint32_t)(rng() % 4096), bd = 64u << (rng() % 5);
+    CHECK(sweep_runlen(count, grid, bd) == std::max<uint64_t>(1, std::min<uint64_t>(32, count / ((uint64_t)grid * bd * 8))));
+  }
+}
+
 int main() {
+  check_fast_limits();
+  check_score_bands();
+  check_objective_sets();
+  check_chunk_states();
+  check_sample_plan();
   check_chunks_per_wave();
   check_geometry();
   check_binomials();

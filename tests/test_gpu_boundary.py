@@ -275,6 +275,38 @@ def test_sweep_split_bounds():
     assert got.tops == [[tuple(r) for r in t] for t in fx["tops"]]
 
 
+def test_group_kernel_exact_with_32_bit_moments_and_64_bit_v():
+    """The s32 && !v32 boundary of the group kernel's selection (ADVICE r06
+    item 4; bote_host.cpp fast_limits): a planet whose sums of squares fit 32
+    bits while V = cnt s2 - s1^2 does not, so the SI kernels (V in 32 bits)
+    must not run.  Twice the synthetic R=128 planet, all 128 clients, the
+    first 24 regions as servers (10,626 and 346,104 configs; groups longer
+    than 64 ranks, so multi-step groups occur): the group kernel's valid
+    count, digest and every top-K list equal the generic kernel's.
+    tests/native/host_check.cpp pins that these numbers give v32 = 0."""
+    base = Planet.synthetic(128)
+    p = Planet(base.names, 2 * base.lat)
+    nc, mx = 128, int(p.lat.max())
+    assert nc * mx >= 2**16, "precondition: V does not fit 32 bits (v32 = 0)"
+    assert nc * (2 * mx) ** 2 < 2**32 and 3 * nc * mx < 2**24, "precondition: the moments do (s32 = 1)"
+    dp = DevicePlanet(p)
+    srv = np.arange(24, dtype=np.uint32)
+    cli = np.arange(128, dtype=np.uint32)
+    for n in (4, 7):
+        got = {}
+        for kernel in ("group", "generic"):
+            sw = Sweep(dp, srv, cli, n, DEFAULT_OBJECTIVES, K=100, ranking=DEFAULT_RANKING, digest=True,
+                       kernel=kernel)
+            assert sw.kernel_path() == kernel
+            sw.launch()
+            got[kernel] = sw.result()
+        g, e = got["group"], got["generic"]
+        assert g.valid == e.valid and g.digest == e.digest, n
+        assert len(g.tops) == len(DEFAULT_OBJECTIVES)
+        for o in range(len(DEFAULT_OBJECTIVES)):
+            assert g.tops[o] == e.tops[o], f"n={n} objective {o}"
+
+
 def test_step_overhead_outside_the_sweep_kernel():
     """Guard rail (the per-step cost outside the sweep kernel grew
     4.5x unnoticed): back-to-back full R=64 n=7 sweeps on one stream, each
