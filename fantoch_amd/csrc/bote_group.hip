@@ -420,11 +420,13 @@ __device__ __forceinline__ int cov2_sign(float Vx, uint32_t Sx, float Vy, uint32
 
 // The validity form (cov_f >= cov_a): the same band, decided with one
 // product per side, x (1 - 2^-18) >= y and x < y (1 - 2^-18), so that both V
-// zero (COV 0 >= COV 0) is decided 1 by the screen itself
+// zero (COV 0 >= COV 0) is decided 1 by the screen itself.  fy2 is (float)Sy
+// squared, from the caller: af1's is shared with the COV af1 objective screen
 template <class FX, class FY>
-__device__ __forceinline__ int cov2_sign_ge(float Vx, uint32_t Sx, float Vy, uint32_t Sy, const FX& dVx, const FY& dVy) {
-  const float fx = (float)Sx, fy = (float)Sy;
-  const float x = Vx * (fy * fy), y = Vy * (fx * fx);
+__device__ __forceinline__ int cov2_sign_ge(float Vx, uint32_t Sx, float Vy, uint32_t Sy, float fy2, const FX& dVx,
+                                            const FY& dVy) {
+  const float fx = (float)Sx;
+  const float x = Vx * fy2, y = Vy * (fx * fx);
   constexpr float c = 1.0f - 0x1p-18f;
   if (x * c >= y) return 1;
   if (x < y * c) return -1;
@@ -1634,44 +1636,48 @@ __global__ void __launch_bounds__(XK ? GROUP_XK_MAX_BD : GROUP_MAX_BD,
                 if constexpr (BIN_FIRST) L2 = L2first;  // (the loop ran before the Q phase)
                 else if (use_lines) L2 = binned_clients(BoolC<true>{}, c0, c1, c2);
                 else L2 = binned_clients(BoolC<false>{}, c0, c1, c2);
-                // the bins (re-zeroed for the next config of this lane), in
-                // packed member pairs laid out as the tables' words wp[t][i]
-                // (members (0, 1), 2, (3, 4), (5, 6) at n = 7; (0, 1), (2, 5),
-                // (3, 4) at n = 6, PAIR2; a lone member's high half is
-                // don't-care: its table word's high half is 0), so
-                // each table's sums are one v_dot2 per word.  The host admits
-                // the bins only where nc max < 2^16 (bote_host.cpp), so every
-                // count, every D1_m and every cnt_m q product fits a u16.
-                constexpr int NW = NWB;
+                // the bins, in packed member pairs laid out as the tables'
+                // words wp[t][i] (members (0, 1), 2, (3, 4), (5, 6) at n = 7;
+                // (0, 1), (2, 5), (3, 4) at n = 6, PAIR2; a lone member's high
+                // half is don't-care: its table word's high half is 0), so each
+                // table's sums are one v_dot2 per word.
                 // the members of word i (low, high; -1: none), as in wp[t][i]
                 auto wlo = [](int i) { return i == 0 ? 0 : (i == 1 ? 2 : 3 + 2 * (i - 2)); };
                 auto whi = [](int i) {
                   return i == 0 ? 1 : (i == 1 ? (PAIR2 ? N - 1 : -1) : (4 + 2 * (i - 2) < N ? 4 + 2 * (i - 2) : -1));
                 };
-                uint32_t wv[N], hv[N];  // bin words; (K_m - m cnt_m) >> 4 = D1_m | cnt_m << 20
+                // Widths.  A bin word is cnt_m << 24 | K_m with K_m = 16 D1_m +
+                // m cnt_m < 2^24 (fast_limits: nc (16 max + 15) < 2^24), so
+                // bin - m cnt = cnt_m << 24 | 16 D1_m and its bits 4..19 are
+                // D1_m: a u16, because the host admits the bins only where
+                // nc max < 2^16 (bote_host.cpp).  cnt_m <= nc < 256 is a byte,
+                // and every cnt_m q product is at most nc max < 2^16.
+                // One LDS exchange per bin returns the word and leaves 0 for
+                // the lane's next config (a read and a write of zero before).
+                uint32_t bin[N], d1[N];  // cnt_m << 24 | K_m;  cnt_m << 20 | D1_m
 #pragma unroll
                 for (int m = 0; m < N; ++m) {
-                  wv[m] = l32(binb + 256u * m);
-                  s32(binb + 256u * m, 0u);
-                  hv[m] = (m ? wv[m] - (uint32_t)m * (wv[m] >> 24) : wv[m]) >> 4;
+                  bin[m] = __hip_atomic_exchange((AS3 uint32_t*)(uintptr_t)(binb + 256u * m), 0u, __ATOMIC_RELAXED,
+                                                 __HIP_MEMORY_SCOPE_WAVEFRONT);
+                  d1[m] = (m ? bin[m] - (uint32_t)m * (bin[m] >> 24) : bin[m]) >> 4;
                 }
-                uint32_t cW[NW], dW[NW];  // (cnt_m | cnt_m' << 16), (D1_m | D1_m' << 16)
+                uint32_t cW[NWB], dW[NWB];  // (cnt_m | cnt_m' << 16), (D1_m | D1_m' << 16): byte 3, bytes 0..1 of each
 #pragma unroll
-                for (int i = 0; i < NW; ++i) {
+                for (int i = 0; i < NWB; ++i) {
                   const int ml = wlo(i), mh = whi(i);
                   if (mh >= 0) {
-                    cW[i] = __builtin_amdgcn_perm(wv[mh], wv[ml], 0x0C070C03u);
-                    dW[i] = __builtin_amdgcn_perm(hv[mh], hv[ml], 0x05040100u);
+                    cW[i] = __builtin_amdgcn_perm(bin[mh], bin[ml], 0x0C070C03u);
+                    dW[i] = __builtin_amdgcn_perm(d1[mh], d1[ml], 0x05040100u);
                   } else {
-                    cW[i] = wv[ml] >> 24;
-                    dW[i] = hv[ml];
+                    cW[i] = bin[ml] >> 24;
+                    dW[i] = d1[ml];
                   }
                 }
                 // L1 = sum_m D1_m; corr = 32 sum_m m D1_m + sum_m m^2 cnt_m
                 // (per word constant pairs; a lone member's high weight 0)
                 uint32_t L1 = 0, corr = 0;
 #pragma unroll
-                for (int i = 0; i < NW; ++i) {
+                for (int i = 0; i < NWB; ++i) {
                   const int ml = wlo(i), mh = whi(i);
                   const uint32_t one = mh >= 0 ? 0x00010001u : 1u;
                   const uint32_t k32 = (uint32_t)(32 * ml) | (mh >= 0 ? (uint32_t)(32 * mh) << 16 : 0u);
@@ -1686,7 +1692,7 @@ __global__ void __launch_bounds__(XK ? GROUP_XK_MAX_BD : GROUP_MAX_BD,
                   // S1 = L1 + sum cnt q;  S2 = L2 + 2 sum D1 q + sum (cnt q) q
                   uint32_t s1 = L1, x = 0, qq = 0;
 #pragma unroll
-                  for (int i = 0; i < NW; ++i) {
+                  for (int i = 0; i < NWB; ++i) {
                     const us2 q = as_us2(wp[t][i]);
                     s1 = __builtin_amdgcn_udot2(as_us2(cW[i]), q, s1, false);
                     x = __builtin_amdgcn_udot2(as_us2(dW[i]), q, x, false);
@@ -1809,6 +1815,10 @@ __global__ void __launch_bounds__(XK ? GROUP_XK_MAX_BD : GROUP_MAX_BD,
             float va1;
             vmom(mom[SLOT_AF1], Va1, va1);
             if constexpr (DEF) {
+              // af1's f32 S^2, outside the divergent validity block: the COV
+              // validity test of f = 1 and the COV af1 objective screen share it
+              const float Sa1f = (float)(uint32_t)mom[SLOT_AF1].s1;
+              const float Sa1sq = Sa1f * Sa1f;
               // ---- compute_score validity (search.rs:421-472), exact.  The
               //      integer mean tests of every f first; the COV tests only
               //      for configs that pass them, and a config is deferred
@@ -1841,19 +1851,21 @@ __global__ void __launch_bounds__(XK ? GROUP_XK_MAX_BD : GROUP_MAX_BD,
                 PSTAT(a, 6, valid);  // COV validity tests
                 if (valid) {
                   // cov_f >= cov_a (min_fairness_fpaxos_improv == 0 on this path):
-                  // cross-multiplied f32 screen, then f64 (cov2_sign)
-                  bool lt = false, amb_c = false;
-#pragma unroll
-                  for (int f = 1; f <= 2; ++f) {
-                    if (f > fcap) break;
-                    const Mom& ma = mom[f == 1 ? SLOT_AF1 : SLOT_AF2];
-                    const Mom& mf = mom[f == 1 ? SLOT_FF1 : SLOT_FF2];
-                    uint64_t Va = Va1;
-                    float vaf = va1;
-                    if (f != 1) vmom(ma, Va, vaf);
-                    const int c = cov2_sign_ge(vlead32, (uint32_t)mf.s1, vaf, (uint32_t)ma.s1, [&] { return vcol[lpos]; },
-                                            [&] { return (double)Va; });
-                    lt = lt || c < 0;
+                  // cross-multiplied f32 screen, then f64 (cov2_sign_ge).  f = 2
+                  // only for a lane not already lt at f = 1 (its verdict is
+                  // settled): af2's V and its screen run for those lanes alone
+                  int c = cov2_sign_ge(vlead32, (uint32_t)mom[SLOT_FF1].s1, va1, (uint32_t)mom[SLOT_AF1].s1, Sa1sq,
+                                       [&] { return vcol[lpos]; }, [&] { return (double)Va1; });
+                  bool lt = c < 0, amb_c = c == 0;
+                  if (fcap >= 2 && !lt) {
+                    const Mom& ma = mom[SLOT_AF2];
+                    uint64_t Va2;
+                    float va2;
+                    vmom(ma, Va2, va2);
+                    const float Sa2f = (float)(uint32_t)ma.s1;
+                    c = cov2_sign_ge(vlead32, (uint32_t)mom[SLOT_FF2].s1, va2, (uint32_t)ma.s1, Sa2f * Sa2f,
+                                     [&] { return vcol[lpos]; }, [&] { return (double)Va2; });
+                    lt = c < 0;
                     amb_c = amb_c || c == 0;
                   }
                   valid = !lt && !amb_c;
@@ -1918,8 +1930,7 @@ __global__ void __launch_bounds__(XK ? GROUP_XK_MAX_BD : GROUP_MAX_BD,
                   // superset): V / S^2 <= the threshold key's V / S^2,
                   // cross-multiplied, the threshold's f32 bound from LDS
                   // (cov_tf32; +inf, or a NaN key: every config passes)
-                  const float S = (float)(uint32_t)m.s1;
-                  const bool maybe = !(va1 > __int_as_float(*(volatile int*)(lock + 2)) * (S * S));
+                  const bool maybe = !(va1 > __int_as_float(*(volatile int*)(lock + 2)) * Sa1sq);
                   PSTAT(a, 10, maybe);  // COV af1 key (f64)
                   if (maybe) {
                     ok[3] = true;

@@ -5,13 +5,19 @@ per 64-config step, reconciled against the measured SQ_INSTS_VALU.
       --offload-device-only -S -o kg.s fantoch_amd/csrc/bote_group.hip
   BOTE_PSTATS=<pathstats json> python scripts/class_mix_table.py kg.s ILi7ELb1ELb1ELb1ELb0ELb1E profiles/pmc.json \
       r64n7_n1 > profiles/<tag>_class_mix.md
+  (BOTE_ISA_OBJ=kg.o, the same command with -c -o kg.o instead of -S -o kg.s: inlined helpers at their call lines)
   (optional 5th-7th arguments: R n trips -- the workload, and the client
   loop's unrolled-body trips per step: nq / (2 BIN_UB), two bodies per trip;
   default 64 7 2; the config-5 kernel, -DBOTE_ISA_N6: ... r128n6_n1 128 6 4)
 
-Static: instructions per section (scripts/isa_lines.py markers).  Modelled
-dynamic count per step: every basic block of a per-step section runs once per
-step, except
+Static: instructions per section (scripts/isa_lines.py markers), each
+instruction counted in the section of its own source line (with BOTE_ISA_OBJ,
+an inlined helper's at its call line: scripts/isa_attrib.py).  A basic block
+often holds several sections' code (the packed-Q2 leader choice is scheduled
+into the Q phase's block, the FPaxos and colocated moments into the digest's),
+so only a block's WEIGHT is decided per block, by the section most of its
+lines belong to.  Modelled dynamic count per step: every basic block of a
+per-step section runs once per step, except
   * blocks on the rare paths (f64 arithmetic: COV/mean decisions inside their
     ambiguity bands, the exact leader re-scan, the full score; the deferral
     queue; the block top-K merge under the LDS lock; the sample launch's
@@ -172,10 +178,25 @@ def main():
             i += 1
     static = defaultdict(Counter)
     dyn = defaultdict(Counter)
+
+    def sec_of_line(ln_, dflt):
+        return next((n for n, a, z in secs if a <= ln_ <= z), dflt) if ln_ else dflt
+
     for b in order:
         s = sec_of[b]
         c = Counter(classify(o) for o in blk_ops[b])
-        static[s].update(c)
+        # A block's WEIGHT comes from the block (the section most of its lines
+        # belong to, its rare marks); its instructions are COUNTED in the
+        # section of their own source line.  The scheduler merges neighbouring
+        # sections into one basic block (the packed-Q2 leader choice sits in
+        # the Q phase's block, the FPaxos and colocated moments in the
+        # digest's), and a per-block majority charged all of a block to one
+        # of them: leader choice 0.3 per step, digest 70 (r06_class_mix.md).
+        per_sec = defaultdict(Counter)
+        for ln_, o in blk_opl[b]:
+            per_sec[sec_of_line(ln_, s)][classify(o)] += 1
+        for s_, c_ in per_sec.items():
+            static[s_].update(c_)
         # (top-K blocks made only of header code: the merge's inlined binary searches)
         rare = (b in merge_blk or any(is_rare_op(o) for o in blk_ops[b]) or
                 (s.startswith("top-K") and not own_line[b]))
@@ -211,8 +232,9 @@ def main():
         if os.environ.get("BOTE_MIX_BLOCKS") and w > 0:  # (diagnostics: the weighted blocks)
             print(f"# {b} {s!r} w={w:.3f} " + " ".join(f"{k}={v}" for k, v in sorted(c.items())) +
                   f" lines={sorted(blk_src[b])[:3]}..{sorted(blk_src[b])[-1:]}", file=sys.stderr)
-        for k, v in c.items():
-            dyn[s][k] += w * v
+        for s_, c_ in per_sec.items():
+            for k, v in c_.items():
+                dyn[s_][k] += w * v
         if w > 0 and os.environ.get("BOTE_MIX_LINE"):  # (diagnostics: one line's weighted instructions)
             sel = [o for ln_, o in blk_opl[b] if str(ln_) == os.environ["BOTE_MIX_LINE"]]
             if sel:
