@@ -105,48 +105,77 @@ __host__ __device__ inline uint32_t lines_wave_bytes(const FastArgs& a) {
   return (a.gslots * (a.cq_stride * 8 + 4) + 15) & ~15u;
 }
 
-// region 0: PERM kernels: per wave, gslots client lines of cq_stride
-// quads; otherwise the qtab (N * NLW member planes of 1 << gqsh bytes)
-__host__ __device__ inline size_t group_layout(const FastArgs& a, int N, int NLW, int KQ, bool perm, size_t* off) {
-  size_t o = 0;
-  off[0] = o;
-  o += perm ? (size_t)(a.gbd / 64) * lines_wave_bytes(a) : ((size_t)N * NLW) << a.gqsh;
-  o = (o + 15) & ~(size_t)15;
-  off[1] = o; o += (size_t)a.R * a.cq_stride * 8;
-  off[2] = o; o += a.rq_separate ? (size_t)a.R * a.rq_stride * 8 : 0;
-  off[3] = o; o += (size_t)a.ns * 4;  // srv
-  o = (o + 7) & ~(size_t)7;
-  off[4] = o; o += (size_t)a.ns * 8;  // lrec: (cs1, f32 vcol) per position
-  o = (o + 15) & ~(size_t)15;
-  off[5] = o; o += (size_t)a.ns * 8;                   // cs2
-  off[6] = o; o += (size_t)a.ns * 8;                   // vcol (f64)
-  off[7] = o; o += (size_t)a.ns * 4;                   // vcol32: V as f32 (the screens' leader V)
+// The workgroup's LDS regions (byte offsets, in this order), group_layout
+struct GroupLds {
+  // PERM kernels: per wave, gslots client lines of cq_stride quads;
+  // otherwise the qtab (N * NLW member planes of 1 << gqsh bytes)
+  size_t lines_or_qtab;
+  size_t cqt;     // the client quad matrix (R columns of cq_stride quads)
+  size_t rqt;     // the server quad matrix, where it is a separate one (rq_separate)
+  size_t srv;     // server list: position -> region
+  size_t lrec;    // (cs1, f32 1 / sqrt(vcol)) per position
+  size_t cs2;     // per position, the column's sum of squares
+  size_t vcol;    // per position, the column's V (f64)
+  size_t vcol32;  // V as f32 (the screens' leader V)
   // (binomials stay in global memory: uniform scalar loads, once per group)
-  o = (o + 15) & ~(size_t)15;
-  off[8] = o; o += (size_t)(a.gbd / 64) * gline_bytes(a, N, KQ);  // per-wave group lines
-  o = (o + 15) & ~(size_t)15;
-  off[9] = o; o += (size_t)a.n_obj * a.K * 16;  // top: n_obj lists of K records
-  off[10] = o; o += (size_t)64 * 16;           // cand (one wave's candidates)
-  off[11] = o; o += (size_t)a.K * 16;          // tmp
-  off[12] = o; o += (size_t)MAXOBJ * 16;      // thr
-  off[13] = o; o += 48;                       // lock
+  size_t glines;  // per-wave group lines
+  size_t top;     // n_obj lists of K records
+  size_t cand;    // one wave's candidates
+  size_t tmp;     // a merge's output list (K records)
+  size_t thr;     // per objective, the threshold record
+  size_t lock;    // the block lock and the screens' bounds (LOCK_*)
   // extended key set (PERM kernels): per wave, N member bins of 64 lanes' u32
-  // (the client loop's binned sums, sweep_group_kernel)
-  o = (o + 15) & ~(size_t)15;
-  off[14] = o; o += perm && (a.keys || a.gbins) ? (size_t)(a.gbd / 64) * N * 256 : 0;
+  // (the client loop's binned sums, binned_clients)
+  size_t bins;
   // per thread, its running digest (u64): an LDS add per step instead of a
   // 64-bit accumulator held in registers across the step loop, which the
   // register-bound kernels spilled to scratch and reloaded, added and stored
   // back every step (config 5: the bulk of its scratch write traffic)
-  o = (o + 15) & ~(size_t)15;
-  off[15] = o; o += (size_t)a.gbd * 8;
-  return o;
+  size_t digest;
+  size_t total;
+};
+
+// the words of the lock region
+enum : int {
+  LOCK_MERGE = 0,  // the block's top-K merge lock (wave_topk)
+  LOCK_SCORE = 1,  // the SCORE screen's bound (score_tlo)
+  LOCK_COV = 2,    // the COV af1 screen's bound (cov_tf32, f32 bits)
+};
+
+__host__ __device__ inline GroupLds group_layout(const FastArgs& a, int N, int NLW, int KQ, bool perm) {
+  const auto a16 = [](size_t o) { return (o + 15) & ~(size_t)15; };
+  GroupLds l;
+  size_t o = 0;
+  l.lines_or_qtab = o; o += perm ? (size_t)(a.gbd / 64) * lines_wave_bytes(a) : ((size_t)N * NLW) << a.gqsh;
+  o = a16(o);
+  l.cqt = o; o += (size_t)a.R * a.cq_stride * 8;
+  l.rqt = o; o += a.rq_separate ? (size_t)a.R * a.rq_stride * 8 : 0;
+  l.srv = o; o += (size_t)a.ns * 4;
+  o = (o + 7) & ~(size_t)7;
+  l.lrec = o; o += (size_t)a.ns * 8;
+  o = a16(o);
+  l.cs2 = o; o += (size_t)a.ns * 8;
+  l.vcol = o; o += (size_t)a.ns * 8;
+  l.vcol32 = o; o += (size_t)a.ns * 4;
+  o = a16(o);
+  l.glines = o; o += (size_t)(a.gbd / 64) * gline_bytes(a, N, KQ);
+  o = a16(o);
+  l.top = o; o += (size_t)a.n_obj * a.K * 16;
+  l.cand = o; o += (size_t)64 * 16;
+  l.tmp = o; o += (size_t)a.K * 16;
+  l.thr = o; o += (size_t)MAXOBJ * 16;
+  l.lock = o; o += 48;
+  o = a16(o);
+  l.bins = o; o += perm && (a.keys || a.gbins) ? (size_t)(a.gbd / 64) * N * 256 : 0;
+  o = a16(o);
+  l.digest = o; o += (size_t)a.gbd * 8;
+  l.total = o;
+  return l;
 }
 
 template <int N>
 static size_t group_smem_n(const FastArgs& a) {
-  size_t off[16];
-  return group_layout(a, N, QCfg<N>::NL <= 2 ? 1 : 2, GCfg<N>::KQ, GCfg<N>::PERM, off);
+  return group_layout(a, N, QCfg<N>::NL <= 2 ? 1 : 2, GCfg<N>::KQ, GCfg<N>::PERM).total;
 }
 
 bool group_uses_lines(uint32_t n) {
@@ -267,7 +296,7 @@ __device__ __forceinline__ void merge_lists(const T* A, const T* y, T* L) {
 // 30 (e.s1 - af.s1) is an exact integer (|T| < 2^27), and the config can beat
 // the block list's threshold key only if (double)T >= (tscore - 1e-6) nc,
 // tscore the key's score: for a finite bound b that is T >= ceil(b).  The
-// bound is kept in LDS next to the block lock (lock[1]) and recomputed when the
+// bound is kept in LDS next to the block lock (LOCK_SCORE) and recomputed when the
 // threshold moves (the list's K-th record, under the lock: a few times per
 // block), instead of decoding the key and comparing in f64 every step.  It only
 // rises as the threshold falls, so a stale read is a looser screen.
@@ -286,7 +315,7 @@ __device__ __forceinline__ int32_t score_tlo(uint64_t tkey, uint32_t nc) {
 // The COV-af1 objective's screen bound (DEF kernels: objective 3): its key is
 // the bits of V / S^2 as a double (cov_key), so a config may beat the
 // threshold only if V <= key S^2; f32 with a 2^-10 margin over the screen's
-// rounding, +inf with no threshold (the all-ones key), kept in LDS at lock[2]
+// rounding, +inf with no threshold (the all-ones key), kept in LDS at LOCK_COV
 // like score_tlo.  A NaN bound lets every config through (always safe: the
 // merge is exact).
 __device__ __forceinline__ float cov_tf32(uint64_t tkey) {
@@ -347,7 +376,7 @@ __device__ __forceinline__ void wave_topk(const TopkLds& t, int* lock, uint32_t 
   const uint32_t lane = threadIdx.x & 63;
   const int KL = (int)K;
   if (lane == 0) {
-    while (atomicCAS(lock, 0, 1) != 0) __builtin_amdgcn_s_sleep(2);
+    while (atomicCAS(lock + LOCK_MERGE, 0, 1) != 0) __builtin_amdgcn_s_sleep(2);
   }
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
@@ -390,13 +419,13 @@ __device__ __forceinline__ void wave_topk(const TopkLds& t, int* lock, uint32_t 
     if (lane == 0 && rec_lt(top[K - 1], t.thr[o])) {
       t.thr[o] = top[K - 1];
       // (the DEF kernels' screens of objectives 0, SCORE, and 3, COV af1)
-      if (o == 0) lock[1] = score_tlo(top[K - 1].key, nc);
-      if (o == 3) lock[2] = __float_as_int(cov_tf32(top[K - 1].key));
+      if (o == 0) lock[LOCK_SCORE] = score_tlo(top[K - 1].key, nc);
+      if (o == 3) lock[LOCK_COV] = __float_as_int(cov_tf32(top[K - 1].key));
     }
     wave_sync();
   }
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  if (lane == 0) atomicExch(lock, 0);
+  if (lane == 0) atomicExch(lock + LOCK_MERGE, 0);
 }
 
 // -------------------------------------- exact-order COV comparisons -------
@@ -442,6 +471,76 @@ __device__ __forceinline__ float u64_to_f32(uint64_t x) {
   return __builtin_fmaf((float)(uint32_t)(x >> 32), 0x1p32f, (float)(uint32_t)x);
 }
 
+// ------------------------------------------------- the kernel's context ---
+// The addresses a wave derives once from the arguments (absolute LDS
+// addresses for the lds_* helpers), with the strides and client counts.
+// The kernel fills it in its prologue, each field where the code first needs
+// it (all of them ahead of the staging loops, or the typed LDS pointers and
+// the top-K lists held here too, gave the kernels another register
+// allocation), and hands it to the functions below by const&.
+struct GroupCtx {
+  bool sid;     // servers in region order (srv[p] == p): SI, or FastArgs::srv_identity
+  bool use_rx;  // the position table: a launch argument, compiled in (RXC) on SI kernels
+  uint32_t LB;    // the LDS address of the workgroup's memory
+  uint32_t qtab;  // GroupLds::lines_or_qtab
+  uint32_t cqt, rqt;
+  uint32_t thra;              // the thresholds (GroupLds::thr)
+  uint32_t cstride, rstride;  // bytes per CQT / RQT column
+  uint32_t nc, nq, rem;       // clients: nq full quads and rem more
+  // PERM: this wave's client lines (one per distinct (p1, p2) of a step),
+  // then the pairs' keys (lowtab entries)
+  uint32_t lines, keys;
+  // this wave's group line
+  uint32_t rxt;  // per-position table (RX)
+  uint32_t mfl;  // nearest fixed member per client
+  uint32_t upk;  // packed fixed-row lists
+  uint32_t fS1;  // fixed column sums
+  uint32_t fVf;  // fixed column 1 / sqrt(V) (f32)
+};
+
+// each client's nearest member of a quad, packed (latency << 4 | member):
+// the lane's member-0 column against its client line, or against the other
+// three sources when no line was built
+template <bool LINES>
+__device__ __forceinline__ void nearest_quad(const GroupCtx& cx, uint32_t ll, uint32_t c0, uint32_t c1, uint32_t c2,
+                                             uint32_t g8, us2& lo, us2& hi) {
+  const us2 J1 = {1, 1}, J2 = {2, 2};
+  const uint2 wa = l64(c0 + g8);
+  if constexpr (LINES) {
+    const uint2 wl = l64(ll + g8);
+    lo = pk_min(as_us2(wa.x), as_us2(wl.x));
+    hi = pk_min(as_us2(wa.y), as_us2(wl.y));
+  } else {
+    const uint2 wb = l64(c1 + g8), wc = l64(c2 + g8), wf = l64(cx.mfl + g8);
+    lo = pk_min(pk_min(as_us2(wa.x), as_us2(wb.x) | J1), pk_min(as_us2(wc.x) | J2, as_us2(wf.x)));
+    hi = pk_min(pk_min(as_us2(wa.y), as_us2(wb.y) | J1), pk_min(as_us2(wc.y) | J2, as_us2(wf.y)));
+  }
+}
+
+// two quads at once (g16: a 16-B aligned offset): one ds_read_b128
+// per source (4 LDS cycles for 16 B per lane, where the pair of
+// 8-B reads the compiler would merge into a ds_read2_b64 takes 8;
+// the column stride is an odd number of 16-B units: quad_stride)
+template <bool LINES>
+__device__ __forceinline__ void nearest_quad_pair(const GroupCtx& cx, uint32_t ll, uint32_t c0, uint32_t c1, uint32_t c2,
+                                                  uint32_t g16, us2& lo0, us2& hi0, us2& lo1, us2& hi1) {
+  const us2 J1 = {1, 1}, J2 = {2, 2};
+  const uint4 wa = l128(c0 + g16);
+  if constexpr (LINES) {
+    const uint4 wl = l128(ll + g16);
+    lo0 = pk_min(as_us2(wa.x), as_us2(wl.x));
+    hi0 = pk_min(as_us2(wa.y), as_us2(wl.y));
+    lo1 = pk_min(as_us2(wa.z), as_us2(wl.z));
+    hi1 = pk_min(as_us2(wa.w), as_us2(wl.w));
+  } else {
+    const uint4 wb = l128(c1 + g16), wc = l128(c2 + g16), wf = l128(cx.mfl + g16);
+    lo0 = pk_min(pk_min(as_us2(wa.x), as_us2(wb.x) | J1), pk_min(as_us2(wc.x) | J2, as_us2(wf.x)));
+    hi0 = pk_min(pk_min(as_us2(wa.y), as_us2(wb.y) | J1), pk_min(as_us2(wc.y) | J2, as_us2(wf.y)));
+    lo1 = pk_min(pk_min(as_us2(wa.z), as_us2(wb.z) | J1), pk_min(as_us2(wc.z) | J2, as_us2(wf.z)));
+    hi1 = pk_min(pk_min(as_us2(wa.w), as_us2(wb.w) | J1), pk_min(as_us2(wc.w) | J2, as_us2(wf.w)));
+  }
+}
+
 // ---------------------------------------------------------- the kernel ----
 // DEF: the default objective set (bote.py DEFAULT_OBJECTIVES: SCORE, MEAN af1,
 // MEAN ff1, COV af1, MEAN e), compiled in; otherwise the objectives come from
@@ -484,13 +583,14 @@ template <int N, bool DEF, bool SI, bool RXC, bool XK, bool BN = false>
 __global__ void __launch_bounds__(XK ? GROUP_XK_MAX_BD : GROUP_MAX_BD,
                                   XK ? BOTE_GROUP_WAVES_XK : (GCfg<N>::PERM ? BOTE_GROUP_WAVES_PERM : BOTE_GROUP_WAVES))
     sweep_group_kernel(FastArgs a) {
-  const bool sid = SI || a.srv_identity;
+  GroupCtx cx;
+  cx.sid = SI || a.srv_identity;
   // S32 (the SI kernels; the host admits them only where FastArgs::s32
   // holds): every slot's sum of squares fits 32 bits, so the moments, the
   // leader columns' sums of squares and the digest folds stay 32-bit
   constexpr bool S32 = SI;
   // the position table: a launch argument, compiled in (RXC) on SI kernels
-  const bool use_rx = GCfg<N>::RX && (SI ? RXC : a.grx != 0);
+  cx.use_rx = GCfg<N>::RX && (SI ? RXC : a.grx != 0);
   using QC = QCfg<N>;
   using GC = GCfg<N>;
   constexpr int NL = QC::NL;
@@ -507,39 +607,39 @@ __global__ void __launch_bounds__(XK ? GROUP_XK_MAX_BD : GROUP_MAX_BD,
   using QT = QTab<N, XK>;
   constexpr int NT = QT::NT;  // leaderless tables (PERM: register byte planes); == NL without XK
   extern __shared__ __align__(16) unsigned char smem[];
-  size_t off[16];
-  group_layout(a, N, NLW, KQ, PERM, off);
-  const uint32_t LB = lds_base(smem);
-  const uint32_t qtab = LB + (uint32_t)off[0];
-  const uint32_t cqt = LB + (uint32_t)off[1];
-  const uint32_t rqt = LB + (uint32_t)(a.rq_separate ? off[2] : off[1]);
-  uint32_t* srv = (uint32_t*)(smem + off[3]);
-  uint2* lrec = (uint2*)(smem + off[4]);  // per position: .x column sum S1, .y f32 bits of 1 / sqrt(V)
-  uint64_t* cs2 = (uint64_t*)(smem + off[5]);
-  double* vcol = (double*)(smem + off[6]);
-  float* vcol32 = (float*)(smem + off[7]);
+  const GroupLds off = group_layout(a, N, NLW, KQ, PERM);
+  cx.LB = lds_base(smem);
+  cx.qtab = cx.LB + (uint32_t)off.lines_or_qtab;
+  cx.cqt = cx.LB + (uint32_t)off.cqt;
+  cx.rqt = cx.LB + (uint32_t)(a.rq_separate ? off.rqt : off.cqt);
+  uint32_t* srv = (uint32_t*)(smem + off.srv);
+  uint2* lrec = (uint2*)(smem + off.lrec);  // per position: .x column sum S1, .y f32 bits of 1 / sqrt(V)
+  uint64_t* cs2 = (uint64_t*)(smem + off.cs2);
+  double* vcol = (double*)(smem + off.vcol);
+  float* vcol32 = (float*)(smem + off.vcol32);
   const uint64_t* binom = a.binom;
   TopkLds tk;
-  tk.top = (Rec*)(smem + off[9]);
-  tk.cand = (Rec*)(smem + off[10]);
-  tk.tmp = (Rec*)(smem + off[11]);
-  tk.thr = (Rec*)(smem + off[12]);
-  const uint32_t thra = LB + (uint32_t)off[12];  // (the thresholds' LDS address)
+  tk.top = (Rec*)(smem + off.top);
+  tk.cand = (Rec*)(smem + off.cand);
+  tk.tmp = (Rec*)(smem + off.tmp);
+  tk.thr = (Rec*)(smem + off.thr);
+  cx.thra = cx.LB + (uint32_t)off.thr;
   tk.cnt = nullptr;
-  int* lock = (int*)(smem + off[13]);
+  int* lock = (int*)(smem + off.lock);
   const uint32_t tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, BD = blockDim.x, WPB = BD >> 6;
   const uint32_t qsh = a.gqsh;  // log2 of the qtab plane stride (bytes)
 
-  // ---- stage: quad matrices, server list, binomials; then per-position sums
+  // ---- block_init: stage the quad matrices, the server list, the lists,
+  //      thresholds, bounds, bins and digest slots; then per-position sums
   {
     const uint32_t cw = a.R * a.cq_stride * 2;
     const uint32_t* src = (const uint32_t*)a.cqt;
-    uint32_t* dst = (uint32_t*)(smem + off[1]);
+    uint32_t* dst = (uint32_t*)(smem + off.cqt);
     for (uint32_t i = tid; i < cw; i += BD) dst[i] = src[i];
     if (a.rq_separate) {
       const uint32_t rw = a.R * a.rq_stride * 2;
       const uint32_t* rs = (const uint32_t*)a.rqt;
-      uint32_t* rd = (uint32_t*)(smem + off[2]);
+      uint32_t* rd = (uint32_t*)(smem + off.rqt);
       for (uint32_t i = tid; i < rw; i += BD) rd[i] = rs[i];
     }
   }
@@ -549,9 +649,9 @@ __global__ void __launch_bounds__(XK ? GROUP_XK_MAX_BD : GROUP_MAX_BD,
   // objective's K-th key over the launch range, from the sample launch)
   if (tid < MAXOBJ) tk.thr[tid] = a.tseed && tid < a.n_obj ? Rec{a.tseed[tid], ~0ull} : rec_max();
   if (tid == 0) {
-    lock[0] = 0;
-    lock[1] = score_tlo(a.tseed && a.n_obj ? a.tseed[0] : ~0ull, a.nc);
-    lock[2] = __float_as_int(cov_tf32(a.tseed && a.n_obj > 3 ? a.tseed[3] : ~0ull));
+    lock[LOCK_MERGE] = 0;
+    lock[LOCK_SCORE] = score_tlo(a.tseed && a.n_obj ? a.tseed[0] : ~0ull, a.nc);
+    lock[LOCK_COV] = __float_as_int(cov_tf32(a.tseed && a.n_obj > 3 ? a.tseed[3] : ~0ull));
   }
   // sample launch with a slot per wave: lane o clears the wave's slot of
   // objective o (no memset before the launch); the same lane's atomicMin
@@ -560,13 +660,13 @@ __global__ void __launch_bounds__(XK ? GROUP_XK_MAX_BD : GROUP_MAX_BD,
     a.smin[(size_t)lane * gridDim.x * WPB + (size_t)blockIdx.x * WPB + wid] = ~0ull;
   // BIN: the member bins start at zero (each lane re-zeroes its own after use)
   if constexpr (BIN)
-    for (uint32_t i = tid; i < (BD >> 6) * N * 64; i += BD) ((uint32_t*)(smem + off[14]))[i] = 0;
-  ((uint64_t*)(smem + off[15]))[tid] = 0;  // this thread's digest
+    for (uint32_t i = tid; i < (BD >> 6) * N * 64; i += BD) ((uint32_t*)(smem + off.bins))[i] = 0;
+  ((uint64_t*)(smem + off.digest))[tid] = 0;  // this thread's digest
   __syncthreads();
-  const uint32_t cstride = a.cq_stride * 8;  // bytes per CQT column
-  const uint32_t rstride = a.rq_stride * 8;
+  cx.cstride = a.cq_stride * 8;  // bytes per CQT column
+  cx.rstride = a.rq_stride * 8;
   for (uint32_t i = tid; i < a.ns; i += BD) {
-    const uint32_t col = cqt + srv[i] * cstride;
+    const uint32_t col = cx.cqt + srv[i] * cx.cstride;
     uint64_t c1 = 0, c2 = 0;
     for (uint32_t c = 0; c < a.nc; ++c) {
       uint64_t v = l16(col + 2 * c) >> LAT_SHIFT;
@@ -584,34 +684,38 @@ __global__ void __launch_bounds__(XK ? GROUP_XK_MAX_BD : GROUP_MAX_BD,
   }
   __syncthreads();
 
-  const uint32_t nc = a.nc, nq = nc >> 2, rem = nc & 3;
-  const uint32_t qlane = qtab + tid * 4;
+  cx.nc = a.nc;
+  cx.nq = cx.nc >> 2;
+  cx.rem = cx.nc & 3;
+  const uint32_t qlane = cx.qtab + tid * 4;
   // PERM: this wave's client lines (one per distinct (p1, p2) of a step),
   // then the pairs' keys (lowtab entries)
-  const uint32_t lines = qtab + wid * lines_wave_bytes(a);
-  const uint32_t keys = lines + a.gslots * cstride;
-  const uint32_t gl = LB + (uint32_t)off[8] + wid * gline_bytes(a, N, KQ);  // this wave's group line
-  const uint32_t rxt = gl;                                                 // per-position table (RX)
-  const uint32_t mfl = gl + gline_rx_bytes(a, N);                          // nearest fixed member per client
-  const uint32_t upk = mfl + cstride;                                      // packed fixed-row lists
-  const uint32_t fS1 = upk + FP * KQ * 4;                                  // fixed column sums
-  const uint32_t fVf = fS1 + F * 4;                                        // fixed column 1 / sqrt(V) (f32)
-  const double pnc1 = a.p_fmean * (double)nc, pnc2 = a.p_emean * (double)nc;
+  cx.lines = cx.qtab + wid * lines_wave_bytes(a);
+  cx.keys = cx.lines + a.gslots * cx.cstride;
+  const uint32_t gl = cx.LB + (uint32_t)off.glines + wid * gline_bytes(a, N, KQ);  // this wave's group line
+  cx.rxt = gl;
+  cx.mfl = gl + gline_rx_bytes(a, N);
+  cx.upk = cx.mfl + cx.cstride;
+  cx.fS1 = cx.upk + FP * KQ * 4;
+  cx.fVf = cx.fS1 + F * 4;
+  const double pnc1 = a.p_fmean * (double)cx.nc, pnc2 = a.p_emean * (double)cx.nc;
   // the wave's valid-config count (uniform: a popcount of the valid lanes per
-  // step, scalar adds) and each lane's running digest in LDS (off[15]):
+  // step, scalar adds) and each lane's running digest in LDS (GroupLds::digest):
   // neither holds vector registers across the step loop
   uint64_t valid_cnt = 0;
   // (the slot address is rebuilt at each add from the bins' lane address,
-  // binb = LB + off[14] + 256 N wid + 4 lane, live through the step anyway:
+  // binb = LB + GroupLds::bins + 256 N wid + 4 lane, live through the step anyway:
   // the slot's own address, live across the step loop, was spilled and
   // reloaded from scratch every step)
-  const uint32_t dofs = uni(LB + (uint32_t)off[15] + wid * 512u - 2u * (LB + (uint32_t)off[14] + wid * (N * 256u)));
+  const uint32_t dofs =
+      uni(cx.LB + (uint32_t)off.digest + wid * 512u - 2u * (cx.LB + (uint32_t)off.bins + wid * (N * 256u)));
   auto digest_add = [&](uint32_t binb_, uint64_t d) {
     uint32_t ad;
     asm("v_lshl_add_u32 %0, %1, 1, %2" : "=v"(ad) : "v"(binb_), "s"(dofs));
     __hip_atomic_fetch_add((AS3 uint64_t*)(uintptr_t)ad, d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
   };
 
+  // ---- claim_range: the wave's next range [r, rend) and its chunk.
   // Work: either this wave's equal share of [rb, re), or (nwchunks > 0)
   // chunks of equal estimated cost taken from a ticket counter until none is
   // left.  Rank shares of equal size are not equal work: a group of C(p3, 3)
@@ -649,6 +753,8 @@ __global__ void __launch_bounds__(XK ? GROUP_XK_MAX_BD : GROUP_MAX_BD,
   }
 
   if (r < rend) {
+    // ---- first_group: the fixed positions of the group that holds r, and
+    //      base, the colex rank of that fixed part
     uint32_t hq[F];  // fixed positions p_3 .. p_{N-1} (uniform)
     uint64_t base = 0;
     if (a.wstate && chunk != ~0u) {
@@ -681,17 +787,17 @@ __global__ void __launch_bounds__(XK ? GROUP_XK_MAX_BD : GROUP_MAX_BD,
     for (;;) {
       const uint64_t gend = base + uni64(binom[hq[0] * (N + 1) + 3]);
       PSTAT(a, 12, true);  // groups (precomputes)
-      // ---------------- per-group, wave-uniform precompute -> group line
+      // ---------------- group_precompute: per-group, wave-uniform -> group line
       uint32_t freg[F];
 #pragma unroll
-      for (int k = 0; k < F; ++k) freg[k] = uni(sid ? hq[k] : srv[hq[k]]);
+      for (int k = 0; k < F; ++k) freg[k] = uni(cx.sid ? hq[k] : srv[hq[k]]);
       if (lane < (uint32_t)F) {
         uint32_t pos = 0;
 #pragma unroll
         for (int k = 0; k < F; ++k) pos = lane == (uint32_t)k ? hq[k] : pos;
         const uint2 lr = lrec[pos];
-        s32(fS1 + 4 * lane, lr.x);
-        s32(fVf + 4 * lane, lr.y);
+        s32(cx.fS1 + 4 * lane, lr.x);
+        s32(cx.fVf + 4 * lane, lr.y);
       }
       if (lane < (uint32_t)FP) {
         // rows 2*lane and 2*lane+1: sorted distances to the other fixed
@@ -706,7 +812,7 @@ __global__ void __launch_bounds__(XK ? GROUP_XK_MAX_BD : GROUP_MAX_BD,
 #pragma unroll
           for (int m = 0; m < PF; ++m) {
             uint32_t d = 0xFFFFu;
-            if (m < F && k < (uint32_t)F && (uint32_t)m != k) d = l16(rqt + freg[m < F ? m : 0] * rstride + 2 * rk) >> LAT_SHIFT;
+            if (m < F && k < (uint32_t)F && (uint32_t)m != k) d = l16(cx.rqt + freg[m < F ? m : 0] * cx.rstride + 2 * rk) >> LAT_SHIFT;
             v[h][m] = d;
           }
           sort_network<PF>(v[h]);
@@ -715,36 +821,36 @@ __global__ void __launch_bounds__(XK ? GROUP_XK_MAX_BD : GROUP_MAX_BD,
         for (int i = 0; i < KQ; ++i) {
           const uint32_t lo = i < F - 1 ? v[0][i < PF ? i : 0] : 0xFFFFu;
           const uint32_t hi = i < F - 1 ? v[1][i < PF ? i : 0] : 0xFFFFu;
-          s32(upk + (lane * KQ + i) * 4, lo | (hi << 16));
+          s32(cx.upk + (lane * KQ + i) * 4, lo | (hi << 16));
         }
       }
       // each client's nearest fixed member: latency << 4 | member index (3 + k)
-      for (uint32_t c = lane; c < (nq + 1) * 4; c += 64) {
+      for (uint32_t c = lane; c < (cx.nq + 1) * 4; c += 64) {
         uint32_t key = 3u;
-        if (c < nc) {
+        if (c < cx.nc) {
           key = 0xFFFFu;
 #pragma unroll
-          for (int k = 0; k < F; ++k) key = min(key, l16(cqt + freg[k] * cstride + 2 * c) | (uint32_t)(3 + k));
+          for (int k = 0; k < F; ++k) key = min(key, l16(cx.cqt + freg[k] * cx.cstride + 2 * c) | (uint32_t)(3 + k));
         }
-        s16(mfl + 2 * c, key);
+        s16(cx.mfl + 2 * c, key);
       }
       GASSERT(a, PERM || (tid + 1) * 4 <= (1u << qsh), 6);  // qtab plane holds every thread's word
-      if (use_rx) {
+      if (cx.use_rx) {
         GASSERT(a, hq[0] <= a.ns, 5);  // position table rows (ns x 16 B per wave)
         // positions below the smallest fixed one: sorted distances to the
         // fixed members (row part), the fixed members' distances to x
         // (column part, packed as the fixed-row pairs); absent members INF
         for (uint32_t x = lane; x < hq[0]; x += 64) {
-          const uint32_t rg = sid ? x : srv[x];
+          const uint32_t rg = cx.sid ? x : srv[x];
           uint32_t rf[4], cf[4];
 #pragma unroll
           for (int k = 0; k < 4; ++k) {
             const uint32_t fk = freg[k < F ? k : 0];
-            rf[k] = k < F ? l16(rqt + fk * rstride + 2 * rg) >> LAT_SHIFT : 0xFFFFu;
-            cf[k] = k < F ? l16(rqt + rg * rstride + 2 * fk) >> LAT_SHIFT : 0xFFFFu;
+            rf[k] = k < F ? l16(cx.rqt + fk * cx.rstride + 2 * rg) >> LAT_SHIFT : 0xFFFFu;
+            cf[k] = k < F ? l16(cx.rqt + rg * cx.rstride + 2 * fk) >> LAT_SHIFT : 0xFFFFu;
           }
           sort_network<4>(rf);
-          s128(rxt + 16 * x, make_uint4(rf[0] | (rf[1] << 16), rf[2] | (rf[3] << 16), cf[0] | (cf[1] << 16),
+          s128(cx.rxt + 16 * x, make_uint4(rf[0] | (rf[1] << 16), rf[2] | (rf[3] << 16), cf[0] | (cf[1] << 16),
                                         cf[2] | (cf[3] << 16)));
         }
         // a fixed member's row at its own position (no variable member sits
@@ -760,8 +866,8 @@ __global__ void __launch_bounds__(XK ? GROUP_XK_MAX_BD : GROUP_MAX_BD,
           }
           uint32_t cf[4];
 #pragma unroll
-          for (int k = 0; k < 4; ++k) cf[k] = k < F ? l16(rqt + rj * rstride + 2 * freg[k < F ? k : 0]) >> LAT_SHIFT : 0xFFFFu;
-          s64(rxt + 16 * pj + 8, cf[0] | (cf[1] << 16), cf[2] | (cf[3] << 16));
+          for (int k = 0; k < 4; ++k) cf[k] = k < F ? l16(cx.rqt + rj * cx.rstride + 2 * freg[k < F ? k : 0]) >> LAT_SHIFT : 0xFFFFu;
+          s64(cx.rxt + 16 * pj + 8, cf[0] | (cf[1] << 16), cf[2] | (cf[3] << 16));
         }
       }
       wave_sync();
@@ -796,12 +902,12 @@ __global__ void __launch_bounds__(XK ? GROUP_XK_MAX_BD : GROUP_MAX_BD,
           ok[o] = false;
         }
         const uint64_t rank = r + lane;
-        // ---- PERM: client lines.  Lanes with equal (p1, p2) (consecutive in
+        // ---- build_client_lines (PERM).  Lanes with equal (p1, p2) (consecutive in
         //      colex order; a lane starts a new pair when p0 == 0) share
         //      min(member 1, member 2, nearest fixed) per client, built once
         //      per step, so the client loop merges one lane column into it.
         //      More distinct pairs than slots: the loop merges all four.
-        uint32_t ll = lines;
+        uint32_t ll = cx.lines;
         bool use_lines = false;
         if constexpr (PERM) {
           const uint64_t nk = __ballot(have && ((cur & 0xFFu) == 0 || lane == 0));
@@ -814,25 +920,25 @@ __global__ void __launch_bounds__(XK ? GROUP_XK_MAX_BD : GROUP_MAX_BD,
             const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(nk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)nk, 0));
             const bool starts = (nk >> lane) & 1;
             const uint32_t slot = below + (starts ? 1u : 0u) - 1;
-            ll = lines + slot * cstride;
+            ll = cx.lines + slot * cx.cstride;
             GASSERT(a, !have || slot < a.gslots, 4);  // client-line slot
-            if (starts) s32(keys + 4 * slot, cur);
+            if (starts) s32(cx.keys + 4 * slot, cur);
             wave_sync();
             // then lpl lanes per line (one quad = 4 clients each), 64 / lpl
             // lines per pass
-            const uint32_t nqq = nq + (rem ? 1u : 0u);
+            const uint32_t nqq = cx.nq + (cx.rem ? 1u : 0u);
             const uint32_t lsh = nqq <= 16 ? 3u : (nqq <= 32 ? 4u : 5u), lpl = 1u << lsh;
             const uint32_t li = lane >> lsh, qx = lane & (lpl - 1);
             for (uint32_t sl = 0; sl < nsl; sl += 64u >> lsh) {
               const uint32_t sx = sl + li;
               if (sx < nsl) {
-                const uint32_t k = l32(keys + 4 * sx);
+                const uint32_t k = l32(cx.keys + 4 * sx);
                 const uint32_t p1 = (k >> 8) & 0xFFu, p2 = k >> 16;
-                const uint32_t b1 = cqt + (sid ? p1 : srv[p1]) * cstride;
-                const uint32_t b2 = cqt + (sid ? p2 : srv[p2]) * cstride;
-                const uint32_t dst = lines + sx * cstride;
+                const uint32_t b1 = cx.cqt + (cx.sid ? p1 : srv[p1]) * cx.cstride;
+                const uint32_t b2 = cx.cqt + (cx.sid ? p2 : srv[p2]) * cx.cstride;
+                const uint32_t dst = cx.lines + sx * cx.cstride;
                 for (uint32_t x = qx; x < nqq; x += lpl) {
-                  const uint2 v1 = l64(b1 + 8 * x), v2 = l64(b2 + 8 * x), vf = l64(mfl + 8 * x);
+                  const uint2 v1 = l64(b1 + 8 * x), v2 = l64(b2 + 8 * x), vf = l64(cx.mfl + 8 * x);
                   const us2 lo = pk_min(pk_min(as_us2(v1.x | 0x00010001u), as_us2(v2.x | 0x00020002u)), as_us2(vf.x));
                   const us2 hi = pk_min(pk_min(as_us2(v1.y | 0x00010001u), as_us2(v2.y | 0x00020002u)), as_us2(vf.y));
                   s64(dst + 8 * x, as_u32(lo), as_u32(hi));
@@ -849,11 +955,11 @@ __global__ void __launch_bounds__(XK ? GROUP_XK_MAX_BD : GROUP_MAX_BD,
           pv[2] = cur >> 16;
           GASSERT(a, pv[0] < pv[1] && pv[1] < pv[2] && pv[2] < hq[0], 3);  // variable positions below the fixed ones
 #pragma unroll
-          for (int i = 0; i < 3; ++i) rv[i] = sid ? pv[i] : srv[pv[i]];
+          for (int i = 0; i < 3; ++i) rv[i] = cx.sid ? pv[i] : srv[pv[i]];
           uint32_t cv[3];  // RQT column of each variable member
 #pragma unroll
-          for (int i = 0; i < 3; ++i) cv[i] = __umul24(rv[i], rstride) + rqt;  // (one v_mad_u32_u24)
-          // ---- BIN: the member-binned client loop, one body for both of its
+          for (int i = 0; i < 3; ++i) cv[i] = __umul24(rv[i], cx.rstride) + cx.rqt;  // (one v_mad_u32_u24)
+          // ---- binned_clients (BIN): the member-binned client loop, one body for both of its
           //      places (before the Q phase with BIN_FIRST: it needs only the
           //      members' columns and the client line, and its results are the
           //      lane's bins in LDS and one squared-key sum, so none of the Q
@@ -865,50 +971,10 @@ __global__ void __launch_bounds__(XK ? GROUP_XK_MAX_BD : GROUP_MAX_BD,
           //      member's clients = 16 D1_m + m cnt_m; the squared keys go to a
           //      v_dot2 sum (returned).  The epilogue (below) turns the bins
           //      into every table's sums.
-          const uint32_t binb = LB + (uint32_t)off[14] + wid * (N * 256) + lane * 4;
+          const uint32_t binb = cx.LB + (uint32_t)off.bins + wid * (N * 256) + lane * 4;
           (void)binb;
           auto binned_clients = [&](auto lines_c, uint32_t c0, uint32_t c1, uint32_t c2) -> uint64_t {
-            const us2 K1 = {1, 1}, K2 = {2, 2};
-            // each client's nearest member, packed (latency << 4 | member):
-            // the lane's member-0 column against its client line, or against
-            // the other three sources when no line was built; two quads per
-            // ds_read_b128 (g16: a 16-B aligned offset)
-            auto nearest = [&](uint32_t g8, uint32_t& L, uint32_t& H) {
-              const uint2 wa = l64(c0 + g8);
-              us2 lo, hi;
-              if constexpr (decltype(lines_c)::value) {
-                const uint2 wl = l64(ll + g8);
-                lo = pk_min(as_us2(wa.x), as_us2(wl.x));
-                hi = pk_min(as_us2(wa.y), as_us2(wl.y));
-              } else {
-                const uint2 wb = l64(c1 + g8), wc = l64(c2 + g8), wf = l64(mfl + g8);
-                lo = pk_min(pk_min(as_us2(wa.x), as_us2(wb.x) | K1), pk_min(as_us2(wc.x) | K2, as_us2(wf.x)));
-                hi = pk_min(pk_min(as_us2(wa.y), as_us2(wb.y) | K1), pk_min(as_us2(wc.y) | K2, as_us2(wf.y)));
-              }
-              L = as_u32(lo);
-              H = as_u32(hi);
-            };
-            auto nearest2 = [&](uint32_t g16, uint32_t& L0, uint32_t& H0, uint32_t& L1, uint32_t& H1) {
-              const uint4 wa = l128(c0 + g16);
-              us2 lo0, hi0, lo1, hi1;
-              if constexpr (decltype(lines_c)::value) {
-                const uint4 wl = l128(ll + g16);
-                lo0 = pk_min(as_us2(wa.x), as_us2(wl.x));
-                hi0 = pk_min(as_us2(wa.y), as_us2(wl.y));
-                lo1 = pk_min(as_us2(wa.z), as_us2(wl.z));
-                hi1 = pk_min(as_us2(wa.w), as_us2(wl.w));
-              } else {
-                const uint4 wb = l128(c1 + g16), wc = l128(c2 + g16), wf = l128(mfl + g16);
-                lo0 = pk_min(pk_min(as_us2(wa.x), as_us2(wb.x) | K1), pk_min(as_us2(wc.x) | K2, as_us2(wf.x)));
-                hi0 = pk_min(pk_min(as_us2(wa.y), as_us2(wb.y) | K1), pk_min(as_us2(wc.y) | K2, as_us2(wf.y)));
-                lo1 = pk_min(pk_min(as_us2(wa.z), as_us2(wb.z) | K1), pk_min(as_us2(wc.z) | K2, as_us2(wf.z)));
-                hi1 = pk_min(pk_min(as_us2(wa.w), as_us2(wb.w) | K1), pk_min(as_us2(wc.w) | K2, as_us2(wf.w)));
-              }
-              L0 = as_u32(lo0);
-              H0 = as_u32(hi0);
-              L1 = as_u32(lo1);
-              H1 = as_u32(hi1);
-            };
+            constexpr bool LINES = decltype(lines_c)::value;
             uint32_t s2l = 0;
             uint64_t L2 = 0;
             auto badd = [&](uint32_t addr, uint32_t v) {
@@ -944,7 +1010,8 @@ __global__ void __launch_bounds__(XK ? GROUP_XK_MAX_BD : GROUP_MAX_BD,
             // (the keys of a group of quads are read before any of their bin
             // adds: the compiler cannot tell the bins from the CQT and lines, so
             // it keeps program order between LDS reads and adds)
-            auto quad_bin = [&](uint32_t L, uint32_t H, uint32_t nv) {
+            auto quad_bin = [&](us2 lo, us2 hi, uint32_t nv) {
+              uint32_t L = as_u32(lo), H = as_u32(hi);
 #ifdef BOTE_DEBUG
               GASSERT(a, (L & 15u) < (uint32_t)N && ((L >> 16) & 15u) < (uint32_t)N && (H & 15u) < (uint32_t)N &&
                              ((H >> 16) & 15u) < (uint32_t)N, 8);
@@ -972,14 +1039,15 @@ __global__ void __launch_bounds__(XK ? GROUP_XK_MAX_BD : GROUP_MAX_BD,
               if (nv >= 3) badd(baddr(H & 15u), __builtin_amdgcn_perm(0x01000000u, H, 0x070C0100u));
             };
             // s2l (squared keys) is flushed to 64 bits every k_flush quads
-            constexpr uint32_t UB = decltype(lines_c)::value ? BIN_UB : 2u;
-            const uint32_t nql = ABLATE(a, 1) ? 0u : nq;
+            constexpr uint32_t UB = LINES ? BIN_UB : 2u;
+            const uint32_t nql = ABLATE(a, 1) ? 0u : cx.nq;
             const uint32_t kfl = a.k_flush, fU = kfl / UB ? kfl / UB : 1u;
             uint32_t g = 0, k = 0;
             auto ub_body = [&](uint32_t g0) {
-              uint32_t Lk[UB], Hk[UB];
+              us2 Lk[UB], Hk[UB];
 #pragma unroll
-              for (uint32_t u = 0; u < UB; u += 2) nearest2(g0 * 8 + 8 * u, Lk[u], Hk[u], Lk[u + 1], Hk[u + 1]);
+              for (uint32_t u = 0; u < UB; u += 2)
+                nearest_quad_pair<LINES>(cx, ll, c0, c1, c2, g0 * 8 + 8 * u, Lk[u], Hk[u], Lk[u + 1], Hk[u + 1]);
 #pragma unroll
               for (uint32_t u = 0; u < UB; ++u) quad_bin(Lk[u], Hk[u], 4u);
             };
@@ -996,9 +1064,10 @@ __global__ void __launch_bounds__(XK ? GROUP_XK_MAX_BD : GROUP_MAX_BD,
               for (; g + UB <= nql; g += UB) ub_body(g);
             } else if (kfl >= UB) {
               for (; g + UB <= nql; g += UB) {
-                uint32_t Lk[UB], Hk[UB];
+                us2 Lk[UB], Hk[UB];
 #pragma unroll
-                for (uint32_t u = 0; u < UB; u += 2) nearest2(g * 8 + 8 * u, Lk[u], Hk[u], Lk[u + 1], Hk[u + 1]);
+                for (uint32_t u = 0; u < UB; u += 2)
+                  nearest_quad_pair<LINES>(cx, ll, c0, c1, c2, g * 8 + 8 * u, Lk[u], Hk[u], Lk[u + 1], Hk[u + 1]);
 #pragma unroll
                 for (uint32_t u = 0; u < UB; ++u) quad_bin(Lk[u], Hk[u], 4u);
                 if (++k == fU) {
@@ -1011,23 +1080,23 @@ __global__ void __launch_bounds__(XK ? GROUP_XK_MAX_BD : GROUP_MAX_BD,
               s2l = 0;
             }
             for (; g < nql; ++g) {
-              uint32_t Lk, Hk;
-              nearest(g * 8, Lk, Hk);
+              us2 Lk, Hk;
+              nearest_quad<LINES>(cx, ll, c0, c1, c2, g * 8, Lk, Hk);
               quad_bin(Lk, Hk, 4u);
               L2 += s2l;
               s2l = 0;
             }
-            if (rem && !ABLATE(a, 1)) {
-              uint32_t Lk, Hk;
-              nearest(nq * 8, Lk, Hk);
-              quad_bin(Lk, Hk, rem);
+            if (cx.rem && !ABLATE(a, 1)) {
+              us2 Lk, Hk;
+              nearest_quad<LINES>(cx, ll, c0, c1, c2, cx.nq * 8, Lk, Hk);
+              quad_bin(Lk, Hk, cx.rem);
             }
             return L2 + s2l;
           };
           uint64_t L2first = 0;
           if constexpr (BIN && BIN_FIRST) {
-            const uint32_t f0 = __umul24(rv[0], cstride) + cqt, f1 = __umul24(rv[1], cstride) + cqt,
-                           f2 = __umul24(rv[2], cstride) + cqt;
+            const uint32_t f0 = __umul24(rv[0], cx.cstride) + cx.cqt, f1 = __umul24(rv[1], cx.cstride) + cx.cqt,
+                           f2 = __umul24(rv[2], cx.cstride) + cx.cqt;
             L2first = use_lines ? binned_clients(BoolC<true>{}, f0, f1, f2) : binned_clients(BoolC<false>{}, f0, f1, f2);
           }
           // member m: 0..2 variable, 3.. fixed (config order = ascending positions)
@@ -1089,7 +1158,7 @@ __global__ void __launch_bounds__(XK ? GROUP_XK_MAX_BD : GROUP_MAX_BD,
               }
             }
           };
-          if (use_rx) {
+          if (cx.use_rx) {
             // ---- Q phase from the group's position table: each variable
             //      row = its sorted fixed part + the 2 distances to the other
             //      variable members; each fixed row = the group's sorted
@@ -1100,9 +1169,9 @@ __global__ void __launch_bounds__(XK ? GROUP_XK_MAX_BD : GROUP_MAX_BD,
               X1 = make_uint4(pv[2], pv[0], pv[1], pv[1] ^ pv[2]);
               X2 = make_uint4(pv[1], pv[2], pv[0], pv[0] ^ pv[2]);
             } else {
-              X0 = l128(rxt + 16 * pv[0]);
-              X1 = l128(rxt + 16 * pv[1]);
-              X2 = l128(rxt + 16 * pv[2]);
+              X0 = l128(cx.rxt + 16 * pv[0]);
+              X1 = l128(cx.rxt + 16 * pv[1]);
+              X2 = l128(cx.rxt + 16 * pv[2]);
             }
             {  // rows 0 and 1, packed (lo: member 0, hi: member 1)
               us2 A[4], y[2], L[KQ];
@@ -1143,7 +1212,7 @@ __global__ void __launch_bounds__(XK ? GROUP_XK_MAX_BD : GROUP_MAX_BD,
             for (int pp = 0; pp < FP; ++pp) {
               us2 A[KQ];  // the group's sorted fixed-row lists (uniform)
 #pragma unroll
-              for (int i = 0; i < KQ; ++i) A[i] = as_us2(l32(upk + (pp * KQ + i) * 4));
+              for (int i = 0; i < KQ; ++i) A[i] = as_us2(l32(cx.upk + (pp * KQ + i) * 4));
               const bool has_hi = 2 * pp + 1 < F;
               us2 y[3];  // the 3 lane distances (d(f, m) | d(f', m)), sorted
               y[0] = as_us2(pp == 0 ? X0.z : X0.w);
@@ -1183,7 +1252,7 @@ __global__ void __launch_bounds__(XK ? GROUP_XK_MAX_BD : GROUP_MAX_BD,
               v[1] = (l16(cv[2] + 2 * rv[0]) | (l16(cv[2] + 2 * rv[1]) << 16)) >> LAT_SHIFT;  // d(0,2) | d(1,2)
   #pragma unroll
               for (int k = 0; k < F; ++k) {
-                const uint32_t fc = rqt + freg[k] * rstride;
+                const uint32_t fc = cx.rqt + freg[k] * cx.rstride;
                 v[2 + k] = (l16(fc + 2 * rv[0]) | (l16(fc + 2 * rv[1]) << 16)) >> LAT_SHIFT;
               }
   #pragma unroll
@@ -1196,7 +1265,7 @@ __global__ void __launch_bounds__(XK ? GROUP_XK_MAX_BD : GROUP_MAX_BD,
               v[0] = l16(cv[0] + 2 * rv[2]) >> LAT_SHIFT;
               v[1] = l16(cv[1] + 2 * rv[2]) >> LAT_SHIFT;
   #pragma unroll
-              for (int k = 0; k < F; ++k) v[2 + k] = l16(rqt + freg[k] * rstride + 2 * rv[2]) >> LAT_SHIFT;
+              for (int k = 0; k < F; ++k) v[2 + k] = l16(cx.rqt + freg[k] * cx.rstride + 2 * rv[2]) >> LAT_SHIFT;
   #pragma unroll
               for (int k = N - 1; k < PV; ++k) v[k] = 0xFFFFu;
               if (!ABLATE(a, 32)) sort_network<PV>(v);
@@ -1208,7 +1277,7 @@ __global__ void __launch_bounds__(XK ? GROUP_XK_MAX_BD : GROUP_MAX_BD,
             for (int pp = 0; pp < FP; ++pp) {
               us2 A[KQ];  // the group's sorted fixed-row lists (uniform)
   #pragma unroll
-              for (int i = 0; i < KQ; ++i) A[i] = as_us2(l32(upk + (pp * KQ + i) * 4));
+              for (int i = 0; i < KQ; ++i) A[i] = as_us2(l32(cx.upk + (pp * KQ + i) * 4));
               const bool has_hi = 2 * pp + 1 < F;
               us2 y[3];  // the 3 lane distances, then sorted (3 compare-exchanges)
   #pragma unroll
@@ -1289,8 +1358,8 @@ __global__ void __launch_bounds__(XK ? GROUP_XK_MAX_BD : GROUP_MAX_BD,
           uint2 vrec[3];  // the variable members' (S1, f32 1 / sqrt(V)): one 8-byte LDS read each
 #pragma unroll
           for (int i = 0; i < 3; ++i) vrec[i] = lrec[pv[i]];
-          auto s1_of = [&](int l) { return l < 3 ? vrec[l].x : l32(fS1 + 4 * (l - 3)); };
-          auto wf_of = [&](int l) { return l < 3 ? __uint_as_float(vrec[l].y) : lf32(fVf + 4 * (l - 3)); };
+          auto s1_of = [&](int l) { return l < 3 ? vrec[l].x : l32(cx.fS1 + 4 * (l - 3)); };
+          auto wf_of = [&](int l) { return l < 3 ? __uint_as_float(vrec[l].y) : lf32(cx.fVf + 4 * (l - 3)); };
           auto vf_of = [&](int l) { return (float)vcol[pos_of(l)]; };  // (exact re-scan only)
           // 1 / COV proxy t = S / sqrt(V) = S * w per member in f32 (S exact
           // below 2^24, w and the product one rounding each): within 2^-23
@@ -1314,11 +1383,11 @@ __global__ void __launch_bounds__(XK ? GROUP_XK_MAX_BD : GROUP_MAX_BD,
               const int pi = l < 2 ? 0 : (l == 2 ? 1 : 2 + (l - 3) / 2);
               const bool hi = l < 2 ? l == 1 : (l > 2 && (l - 3) % 2 == 1);
               uint32_t r;
-              if (hi) asm("v_mad_u32_u16 %0, %1, %2, %3 op_sel:[1,0,0,0]" : "=v"(r) : "v"(Q2w[pi]), "s"(nc), "v"(s1_of(l)));
-              else asm("v_mad_u32_u16 %0, %1, %2, %3" : "=v"(r) : "v"(Q2w[pi]), "s"(nc), "v"(s1_of(l)));
+              if (hi) asm("v_mad_u32_u16 %0, %1, %2, %3 op_sel:[1,0,0,0]" : "=v"(r) : "v"(Q2w[pi]), "s"(cx.nc), "v"(s1_of(l)));
+              else asm("v_mad_u32_u16 %0, %1, %2, %3" : "=v"(r) : "v"(Q2w[pi]), "s"(cx.nc), "v"(s1_of(l)));
               return r;
             } else {
-              return s1_of(l) + __umul24(nc, Q2[l]);
+              return s1_of(l) + __umul24(cx.nc, Q2[l]);
             }
           };
           bool amb = false;
@@ -1358,11 +1427,11 @@ __global__ void __launch_bounds__(XK ? GROUP_XK_MAX_BD : GROUP_MAX_BD,
             bi = 0;
             lcode = 0;
             uint32_t bpos = pv[0];
-            uint32_t bS = s1_of(0) + nc * Q2[0];
+            uint32_t bS = s1_of(0) + cx.nc * Q2[0];
             float bV = vf_of(0);
 #pragma unroll
             for (int l = 1; l < N; ++l) {
-              const uint32_t S = s1_of(l) + nc * Q2[l];
+              const uint32_t S = s1_of(l) + cx.nc * Q2[l];
               const float V = vf_of(l);
               if (V == 0.0f && bV == 0.0f) continue;  // both COV exactly 0: keep the first
               const uint32_t pl = pos_of(l);
@@ -1441,7 +1510,7 @@ __global__ void __launch_bounds__(XK ? GROUP_XK_MAX_BD : GROUP_MAX_BD,
                 for (int l = 0; l < N; ++l) {
                   const uint32_t c1 = s1_of(l), c2 = (uint32_t)cs2[pos_of(l)];
                   const uint32_t q = f == 0 ? Q2[l] : Q3[l];
-                  const uint32_t m1 = __umul24(nc, q) + c1;  // (nc, q, c1 + m1 < 2^24)
+                  const uint32_t m1 = __umul24(cx.nc, q) + c1;  // (nc, q, c1 + m1 < 2^24)
                   const uint32_t m2 = __umul24(q, c1 + m1) + c2;
                   hx = digest_fold_leader(hx, f, l, m1, m2);
                   if (f == 0 && m1 < b1) {
@@ -1466,7 +1535,6 @@ __global__ void __launch_bounds__(XK ? GROUP_XK_MAX_BD : GROUP_MAX_BD,
             }
             // ---- Input leaderless: 3 lane columns + the wave's nearest-fixed line
             {
-              const us2 J1 = {1, 1}, J2 = {2, 2};
               // Sums use full-rate 32-bit adds on packed u16 pairs (no half
               // overflows: lat + q < 2^15, and p1 is flushed every g_flush
               // quads), squares the 2-wide dot product (s2, flushed to 64 bits)
@@ -1479,49 +1547,14 @@ __global__ void __launch_bounds__(XK ? GROUP_XK_MAX_BD : GROUP_MAX_BD,
                 s2[t] = 0;
                 p1[t] = 0;
               }
-              const uint32_t c0 = __umul24(rv[0], cstride) + cqt, c1 = __umul24(rv[1], cstride) + cqt,
-                             c2 = __umul24(rv[2], cstride) + cqt;
+              const uint32_t c0 = __umul24(rv[0], cx.cstride) + cx.cqt, c1 = __umul24(rv[1], cx.cstride) + cx.cqt,
+                             c2 = __umul24(rv[2], cx.cstride) + cx.cqt;
               // (m << qsh) + qlane in one instruction (the compiler would
               // otherwise re-associate it into shift, and, add)
               auto qaddr = [&](uint32_t m) {
                 uint32_t r;
                 asm("v_lshl_add_u32 %0, %1, %2, %3" : "=v"(r) : "v"(m), "s"(qsh), "v"(qlane));
                 return r;
-              };
-              // each client's nearest member, packed (latency << 4 | member):
-              // the lane's member-0 column against its client line, or
-              // against the other three sources when no line was built
-              auto nearest = [&](auto lines_c, uint32_t g8, us2& lo, us2& hi) {
-                const uint2 wa = l64(c0 + g8);
-                if constexpr (decltype(lines_c)::value) {
-                  const uint2 wl = l64(ll + g8);
-                  lo = pk_min(as_us2(wa.x), as_us2(wl.x));
-                  hi = pk_min(as_us2(wa.y), as_us2(wl.y));
-                } else {
-                  const uint2 wb = l64(c1 + g8), wc = l64(c2 + g8), wf = l64(mfl + g8);
-                  lo = pk_min(pk_min(as_us2(wa.x), as_us2(wb.x) | J1), pk_min(as_us2(wc.x) | J2, as_us2(wf.x)));
-                  hi = pk_min(pk_min(as_us2(wa.y), as_us2(wb.y) | J1), pk_min(as_us2(wc.y) | J2, as_us2(wf.y)));
-                }
-              };
-              // two quads at once (g16: a 16-B aligned offset): one ds_read_b128
-              // per source (4 LDS cycles for 16 B per lane, where the pair of
-              // 8-B reads the compiler would merge into a ds_read2_b64 takes 8;
-              // the column stride is an odd number of 16-B units: quad_stride)
-              auto nearest2 = [&](auto lines_c, uint32_t g16, us2& lo0, us2& hi0, us2& lo1, us2& hi1) {
-                const uint4 wa = l128(c0 + g16);
-                if constexpr (decltype(lines_c)::value) {
-                  const uint4 wl = l128(ll + g16);
-                  lo0 = pk_min(as_us2(wa.x), as_us2(wl.x));
-                  hi0 = pk_min(as_us2(wa.y), as_us2(wl.y));
-                  lo1 = pk_min(as_us2(wa.z), as_us2(wl.z));
-                  hi1 = pk_min(as_us2(wa.w), as_us2(wl.w));
-                } else {
-                  const uint4 wb = l128(c1 + g16), wc = l128(c2 + g16), wf = l128(mfl + g16);
-                  lo0 = pk_min(pk_min(as_us2(wa.x), as_us2(wb.x) | J1), pk_min(as_us2(wc.x) | J2, as_us2(wf.x)));
-                  hi0 = pk_min(pk_min(as_us2(wa.y), as_us2(wb.y) | J1), pk_min(as_us2(wc.y) | J2, as_us2(wf.y)));
-                  lo1 = pk_min(pk_min(as_us2(wa.z), as_us2(wb.z) | J1), pk_min(as_us2(wc.z) | J2, as_us2(wf.z)));
-                  hi1 = pk_min(pk_min(as_us2(wa.w), as_us2(wb.w) | J1), pk_min(as_us2(wc.w) | J2, as_us2(wf.w)));
-                }
               };
               auto quad_at = [&](us2 lo, us2 hi, uint32_t mlo, uint32_t mhi) {
                 const uint32_t L = as_u32(lo), H = as_u32(hi);
@@ -1574,12 +1607,12 @@ __global__ void __launch_bounds__(XK ? GROUP_XK_MAX_BD : GROUP_MAX_BD,
               };
               auto quad = [&](auto lines_c, uint32_t g8, uint32_t mlo, uint32_t mhi) {
                 us2 lo, hi;
-                nearest(lines_c, g8, lo, hi);
+                nearest_quad<decltype(lines_c)::value>(cx, ll, c0, c1, c2, g8, lo, hi);
                 quad_at(lo, hi, mlo, mhi);
               };
               auto quad2 = [&](auto lines_c, uint32_t g16) {
                 us2 lo0, hi0, lo1, hi1;
-                nearest2(lines_c, g16, lo0, hi0, lo1, hi1);
+                nearest_quad_pair<decltype(lines_c)::value>(cx, ll, c0, c1, c2, g16, lo0, hi0, lo1, hi1);
                 quad_at(lo0, hi0, ~0u, ~0u);
                 quad_at(lo1, hi1, ~0u, ~0u);
               };
@@ -1592,7 +1625,7 @@ __global__ void __launch_bounds__(XK ? GROUP_XK_MAX_BD : GROUP_MAX_BD,
                   p1[t] = 0;
                 }
               };
-              const uint32_t nql = ABLATE(a, 1) ? 0u : nq;
+              const uint32_t nql = ABLATE(a, 1) ? 0u : cx.nq;
               // 4 quads per iteration (constant offsets fold into the ds_read
               // offset fields); s2 is flushed to 64 bits every s2_flush quads
               // (XK: 2 quads per iteration; its 4 tables' temporaries of 4
@@ -1618,8 +1651,8 @@ __global__ void __launch_bounds__(XK ? GROUP_XK_MAX_BD : GROUP_MAX_BD,
                   for (g = g0; g < ge; ++g) quad(lines_c, g * 8, ~0u, ~0u);
                   flush();
                 }
-                if (rem && !ABLATE(a, 1)) {
-                  quad(lines_c, nq * 8, rem >= 2 ? ~0u : 0x0000FFFFu, rem == 3 ? 0x0000FFFFu : 0u);
+                if (cx.rem && !ABLATE(a, 1)) {
+                  quad(lines_c, cx.nq * 8, cx.rem >= 2 ? ~0u : 0x0000FFFFu, cx.rem == 3 ? 0x0000FFFFu : 0u);
                   flush();
                 }
               };
@@ -1714,9 +1747,9 @@ __global__ void __launch_bounds__(XK ? GROUP_XK_MAX_BD : GROUP_MAX_BD,
                   S2[t] = (uint64_t)S1[t] * S1[t] + 12345u;
                 }
               }
-              mom[SLOT_AF1] = Mom{S1[QC::idx_a1], S2[QC::idx_a1], nc};
-              mom[SLOT_AF2] = Mom{S1[QC::idx_a2], S2[QC::idx_a2], nc};
-              mom[SLOT_E] = Mom{S1[QC::idx_e], S2[QC::idx_e], nc};
+              mom[SLOT_AF1] = Mom{S1[QC::idx_a1], S2[QC::idx_a1], cx.nc};
+              mom[SLOT_AF2] = Mom{S1[QC::idx_a2], S2[QC::idx_a2], cx.nc};
+              mom[SLOT_E] = Mom{S1[QC::idx_e], S2[QC::idx_e], cx.nc};
               if constexpr (XK) {
                 // Tempo tiny (2f) and write (f + 1) quorums, Input: slots 10..13
                 constexpr int t2 = QT::idx(2), t3 = QT::idx(3), t4 = QT::idx(4);
@@ -1734,27 +1767,27 @@ __global__ void __launch_bounds__(XK ? GROUP_XK_MAX_BD : GROUP_MAX_BD,
               // sum (L + q) and sum (L + q)^2 = c2 + q (c1 + S1), in 32 bits,
               // with 24-bit multiplies (FastArgs::s32: c1 + S1 <= 3 nc max < 2^24)
               const uint32_t lc2 = (uint32_t)cs2[lpos];
-              const uint32_t m2 = __umul24(nc, lq2) + lc1, m3 = __umul24(nc, lq3) + lc1;
-              mom[SLOT_FF1] = Mom{m2, __umul24(lq2, lc1 + m2) + lc2, nc};
-              mom[SLOT_FF2] = Mom{m3, __umul24(lq3, lc1 + m3) + lc2, nc};
+              const uint32_t m2 = __umul24(cx.nc, lq2) + lc1, m3 = __umul24(cx.nc, lq3) + lc1;
+              mom[SLOT_FF1] = Mom{m2, __umul24(lq2, lc1 + m2) + lc2, cx.nc};
+              mom[SLOT_FF2] = Mom{m3, __umul24(lq3, lc1 + m3) + lc2, cx.nc};
             } else {
               const uint64_t lc2 = cs2[lpos];
-              mom[SLOT_FF1] = leader_mom(lc1, lc2, nc, lq2);
-              mom[SLOT_FF2] = leader_mom(lc1, lc2, nc, lq3);
+              mom[SLOT_FF1] = leader_mom(lc1, lc2, cx.nc, lq2);
+              mom[SLOT_FF2] = leader_mom(lc1, lc2, cx.nc, lq3);
             }
             // ---- Colocated: FPaxos reads the leader's column of the config
             //      submatrix; leaderless values are the members' own quorums
             {
-              const uint32_t lcol = __umul24(lreg, rstride) + rqt;
+              const uint32_t lcol = __umul24(lreg, cx.rstride) + cx.rqt;
               // sum_k (v_k + q) and sum_k (v_k + q)^2 from sum v and sum v^2
               uint32_t sv = 0, sv2 = 0;
               int k0 = 0;
-              if (use_rx) {
+              if (cx.use_rx) {
                 // the fixed members' part from the column words of the
                 // leader's position-table row (packed u16 pairs: v_dot2; the
                 // pad halves past F are INF and masked off), then the three
                 // variable members' distances
-                const uint2 cw = l64(rxt + 16 * lpos + 8);
+                const uint2 cw = l64(cx.rxt + 16 * lpos + 8);
                 const uint32_t w0 = F >= 2 ? cw.x : (cw.x & 0xFFFFu), w1 = F >= 4 ? cw.y : (cw.y & 0xFFFFu);
                 sv = __builtin_amdgcn_udot2(as_us2(w0), as_us2(0x00010001u), 0u, false);
                 sv2 = __builtin_amdgcn_udot2(as_us2(w0), as_us2(w0), 0u, false);
@@ -1905,7 +1938,7 @@ __global__ void __launch_bounds__(XK ? GROUP_XK_MAX_BD : GROUP_MAX_BD,
                     T += (int32_t)(uint32_t)mom[f == 1 ? SLOT_FF1 : SLOT_FF2].s1 - a1 +
                          30 * ((int32_t)(uint32_t)mom[SLOT_E].s1 - a1);
                   }
-                  const bool maybe = T >= *(volatile int*)(lock + 1);  // (score_tlo)
+                  const bool maybe = T >= *(volatile int*)(lock + LOCK_SCORE);  // (score_tlo)
                   PSTAT(a, 9, maybe);  // f64 score
                   if (maybe) {
                     double score = 0.0;
@@ -1930,7 +1963,7 @@ __global__ void __launch_bounds__(XK ? GROUP_XK_MAX_BD : GROUP_MAX_BD,
                   // superset): V / S^2 <= the threshold key's V / S^2,
                   // cross-multiplied, the threshold's f32 bound from LDS
                   // (cov_tf32; +inf, or a NaN key: every config passes)
-                  const bool maybe = !(va1 > __int_as_float(*(volatile int*)(lock + 2)) * Sa1sq);
+                  const bool maybe = !(va1 > __int_as_float(*(volatile int*)(lock + LOCK_COV)) * Sa1sq);
                   PSTAT(a, 10, maybe);  // COV af1 key (f64)
                   if (maybe) {
                     ok[3] = true;
@@ -1948,7 +1981,7 @@ __global__ void __launch_bounds__(XK ? GROUP_XK_MAX_BD : GROUP_MAX_BD,
           }
         }
         valid_cnt += (uint64_t)__popcll(__ballot(vflag));  // (every lane active here: a uniform count)
-        // ---- top-K: lock-free screen, exact merge under the block lock
+        // ---- sample_min, or topk_screen: lock-free screen, exact merge under the block lock
         if (a.smin) {
           // sample launch: per objective the least key of this chunk's configs
           const int nobj = XK ? 8 : (DEF ? 5 : a.n_obj);
@@ -1983,7 +2016,7 @@ __global__ void __launch_bounds__(XK ? GROUP_XK_MAX_BD : GROUP_MAX_BD,
 #pragma unroll
           for (int o = 0; o < MAXOBJ; ++o)
             if (o < nobj) {
-              const uint2 t = l64(thra + 16u * o);
+              const uint2 t = l64(cx.thra + 16u * o);
               th[o] = ((uint64_t)t.y << 32) | t.x;
             }
           bool pass = false;
@@ -2000,7 +2033,7 @@ __global__ void __launch_bounds__(XK ? GROUP_XK_MAX_BD : GROUP_MAX_BD,
       // range bounds its K-th key, and a sample across many small groups,
       // as at rank 0, cost one precompute each: the launch's slowest wave)
       if (r >= rend || a.smin) break;
-      // ---------------- next group: colex successor of the fixed positions
+      // ---------------- next_group: colex successor of the fixed positions
       // (a combination of {3 .. ns-1}; the smallest fixed position is >= 3)
       {
         int js = F;
@@ -2023,9 +2056,10 @@ __global__ void __launch_bounds__(XK ? GROUP_XK_MAX_BD : GROUP_MAX_BD,
   }
   wave_sync();  // (the next chunk rewrites the group line)
   }
+  // ---- write_lists: the counters, then the block's lists
   if (a.smin) return;  // (the sample launch: no counters, no lists; no barrier follows)
   if (valid_cnt && lane == 0) atomicAdd(&a.out_counters[0], (unsigned long long)valid_cnt);  // (uniform)
-  const uint64_t digest = *(const AS3 uint64_t*)(uintptr_t)(LB + (uint32_t)off[15] + tid * 8);
+  const uint64_t digest = *(const AS3 uint64_t*)(uintptr_t)(cx.LB + (uint32_t)off.digest + tid * 8);
   if (digest) atomicAdd(&a.out_counters[1], (unsigned long long)digest);
   __syncthreads();
   Rec* dst = a.out_top + (size_t)blockIdx.x * a.n_obj * KP;

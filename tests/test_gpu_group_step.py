@@ -98,6 +98,17 @@ def test_other_register_lookup_kernels(planets, n):
     _check(planets[16], 16, np.arange(16, dtype=np.uint32), n)
 
 
+@pytest.mark.parametrize("nc", [16, 13])
+def test_three_table_qtab_kernel(planets, nc):
+    """n = 10 is the first config size with three leaderless quorum tables
+    (qe = 8 next to qa1 = 6 and qa2 = 7): the LDS qtab path with its second
+    member plane.  All C(16, 10) = 8,008 configs, whole quads and a last quad
+    of one client; 282 of them are valid at nc = 16 (CPU oracle)."""
+    valid, _, tops = _check(planets[16], 16, np.arange(nc, dtype=np.uint32), 10)
+    if nc == 16:
+        assert valid > 0 and all(tops)
+
+
 @pytest.mark.parametrize("nc", [33, 34, 35, 36])
 def test_binned_client_loop(planets, nc):
     """32 clients and more run the member-binned client loop, whose epilogue
