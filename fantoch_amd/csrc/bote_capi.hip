@@ -3,7 +3,7 @@
 // Host responsibilities only: argument validation (the reference panics, we
 // return BOTE_E_* codes), device buffers, launch geometry and the merge chain.
 // Every computation of latencies, quorums, leaders, histograms moments, scores
-// and top-K selection runs on the device (bote_kernels.hip).
+// and top-K selection runs on the device (the bote_*.hip kernel files).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -1130,20 +1130,20 @@ static int merge_chain(bote_sweep* s, uint32_t lists, hipStream_t st, const unsi
     int b = 0;
     if (sel) {
       Rec* dst = lists > bote::G_MERGE_LISTS || alt_lists > bote::G_MERGE_LISTS ? bufs[b] : rec_out;
-      HIP_TRY(bote::launch_merge_sel(src, lists, s->top_alt.as<Rec>(), alt_lists, lstride, sel, QUEUE_CAP, dst, lstride,
-                                     s->n_obj, st));
+      HIP_TRY(bote::launch_merge(src, lists, s->top_alt.as<Rec>(), alt_lists, lstride, sel, QUEUE_CAP, dst, lstride,
+                                 s->n_obj, st));
       lists = (std::max(lists, alt_lists) + bote::G_MERGE_LISTS - 1) / bote::G_MERGE_LISTS;
       src = dst;
       b ^= 1;
       if (dst == rec_out) lists = 0;
     }
     while (lists > bote::G_MERGE_LISTS) {
-      HIP_TRY(bote::launch_merge(src, lists, lstride, bufs[b], lstride, s->n_obj, st));
+      HIP_TRY(bote::launch_merge(src, lists, nullptr, 0, lstride, nullptr, 0, bufs[b], lstride, s->n_obj, st));
       src = bufs[b];
       b ^= 1;
       lists = (lists + bote::G_MERGE_LISTS - 1) / bote::G_MERGE_LISTS;
     }
-    if (lists) HIP_TRY(bote::launch_merge(src, lists, lstride, rec_out, lstride, s->n_obj, st));
+    if (lists) HIP_TRY(bote::launch_merge(src, lists, nullptr, 0, lstride, nullptr, 0, rec_out, lstride, s->n_obj, st));
   }
   if (sel) {
     HIP_TRY(bote::launch_pick_counters(s->counters.as<unsigned long long>(), s->counters_alt.as<unsigned long long>(),
@@ -1390,7 +1390,8 @@ int bote_merge_device(const bote_sweep* s, const void* src, uint32_t n_shards, v
   hipStream_t st = (hipStream_t)hip_stream;
   const uint64_t bstride = s->result_bytes() / 16;  // records per block
   const uint64_t lstride = (uint64_t)s->n_obj * bote::KP;
-  if (s->n_obj) HIP_TRY(bote::launch_merge((const Rec*)src, n_shards, bstride, (Rec*)dst, lstride, s->n_obj, st));
+  if (s->n_obj)
+    HIP_TRY(bote::launch_merge((const Rec*)src, n_shards, nullptr, 0, bstride, nullptr, 0, (Rec*)dst, lstride, s->n_obj, st));
   HIP_TRY(bote::launch_sum_counters((const uint64_t*)src, n_shards, bstride * 2, lstride * 2,
                                     (uint64_t*)dst + lstride * 2, st));
   return BOTE_OK;
@@ -1729,6 +1730,24 @@ int bote_search_topk(const bote_planet* const* planets, uint32_t n_devices, cons
   search_free(h);
   if (rc) g_err = err;
   return rc;
+}
+
+// test entry, not part of the ABI: launch_seed over caller-supplied keys
+// (keys: n_obj rows of nsamp, row o at keys[o * nsamp]; out: n_obj keys)
+int bote_test_seed(int device, const uint64_t* keys, uint32_t nsamp, uint32_t n_obj, uint32_t K, uint64_t* out) {
+  DevGuard dev_guard;  // the caller's current device is restored on return
+  if (!keys || !out || nsamp == 0 || n_obj == 0) return fail(BOTE_E_ARG, "bad seed test arguments");
+  if (n_obj > (uint32_t)bote::MAXOBJ) return fail(BOTE_E_RANGE, "at most 8 rows per seed launch");
+  HIP_TRY(hipSetDevice(device));
+  DBuf din, dout;
+  const size_t nb = (size_t)n_obj * nsamp * 8;
+  if (din.alloc(nb) != hipSuccess || dout.alloc((size_t)n_obj * 8) != hipSuccess)
+    return fail(BOTE_E_NOMEM, "hipMalloc seed test buffers");
+  HIP_TRY(hipMemcpy(din.p, keys, nb, hipMemcpyHostToDevice));
+  HIP_TRY(bote::launch_seed(din.as<uint64_t>(), nsamp, n_obj, K, dout.as<uint64_t>(), nullptr));
+  HIP_TRY(hipMemcpy(out, dout.p, (size_t)n_obj * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(hipDeviceSynchronize());
+  return BOTE_OK;
 }
 
 }  // extern "C"

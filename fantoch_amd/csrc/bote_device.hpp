@@ -147,6 +147,12 @@ struct Mom {
   uint32_t cnt;
 };
 
+// FPaxos Input moments from the leader column's sums (Bote::leader,
+// fantoch_bote/src/lib.rs:67-89): sum_c (L + q) and sum_c (L + q)^2.
+__device__ __forceinline__ Mom leader_mom(uint64_t c1, uint64_t c2, uint32_t nc, uint64_t q) {
+  return Mom{c1 + (uint64_t)nc * q, c2 + 2ull * q * c1 + (uint64_t)nc * q * q, nc};
+}
+
 struct U128 {
   uint64_t hi, lo;
 };

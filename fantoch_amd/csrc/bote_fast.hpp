@@ -21,12 +21,6 @@ __device__ __forceinline__ void defer_rank(const FastArgs& a, uint64_t rank) {
   if (q < a.queue_cap) a.queue[q] = rank;
 }
 
-// FPaxos Input moments from the leader column's sums (Bote::leader,
-// fantoch_bote/src/lib.rs:67-89): sum_c (L + q) and sum_c (L + q)^2.
-__device__ __forceinline__ Mom leader_mom(uint64_t c1, uint64_t c2, uint32_t nc, uint64_t q) {
-  return Mom{c1 + (uint64_t)nc * q, c2 + 2ull * q * c1 + (uint64_t)nc * q * q, nc};
-}
-
 // compute_score validity (search.rs:421-472), digest and objective keys of one
 // evaluated configuration.  `vcol_lead` is V of the leader's column (variance
 // is shift invariant, so it is also V of ff1 and ff2).  `thr` holds the

@@ -1,5 +1,5 @@
 // bote_kernels.hpp — launch interface between the C ABI (bote_capi.hip) and
-// the gfx950 kernels (bote_kernels.hip).
+// the gfx950 kernels (one section per kernel file).
 #pragma once
 #include "bote_device.hpp"
 
@@ -232,14 +232,21 @@ int group_occupancy(const FastArgs& a, uint32_t n, size_t shm, bool def_objectiv
 hipError_t launch_group(const FastArgs& a, uint32_t n, bool def_objectives, uint32_t grid, size_t shm, hipStream_t st,
                         hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
 
+// ---- generic exact kernel (bote_kernels.hip)
 size_t eval_smem_bytes(const EvalArgs& a, uint32_t n, uint32_t bd, bool topk);
 int eval_occupancy(uint32_t n, bool full, uint32_t bd, size_t shm, bool keys = false);
 hipError_t launch_eval(const EvalArgs& a, uint32_t n, bool full, uint32_t grid, uint32_t bd, size_t shm,
                        hipStream_t st);
-hipError_t launch_merge(const Rec* src, uint32_t n_lists, uint64_t list_stride, Rec* dst, uint64_t out_stride,
-                        uint32_t n_obj, hipStream_t st);
-// Merge whose input is chosen on the device: `alt` (alt_lists lists) when
-// *sel > cap, else `src` (n_lists lists).
+
+// ---- top-K lists: merge, seed, counters (bote_merge.hip)
+// One level of the merge tree: every G_MERGE_LISTS lists of `src` (n_lists
+// lists, list i of objective o at src[i * list_stride + o * KP]) into one at
+// dst[g * out_stride + o * KP].  With `sel` the input is chosen on the
+// device: `alt` (alt_lists lists) when *sel > cap, else `src`; a plain merge
+// passes null, 0 for alt, alt_lists, sel and cap.
+hipError_t launch_merge(const Rec* src, uint32_t n_lists, const Rec* alt, uint32_t alt_lists, uint64_t list_stride,
+                        const unsigned long long* sel, uint64_t cap, Rec* dst, uint64_t out_stride, uint32_t n_obj,
+                        hipStream_t st);
 constexpr uint32_t WIDE_MERGE_LISTS = 4096;
 // one launch for a sweep's block lists (<= WIDE_MERGE_LISTS lists): the K least per
 // objective into dst[o * KP] (sel/alt/cap: the overflow fallback's choice)
@@ -249,19 +256,19 @@ hipError_t launch_merge_wide(const Rec* src, uint32_t n_lists, const Rec* alt, u
                              const unsigned long long* sel, uint64_t cap, const unsigned long long* kbound, Rec* dst,
                              uint32_t n_obj, uint32_t K, const unsigned long long* csrc, const unsigned long long* calt,
                              uint64_t* cdst, hipStream_t st);
-hipError_t launch_merge_sel(const Rec* src, uint32_t n_lists, const Rec* alt, uint32_t alt_lists, uint64_t list_stride,
-                            const unsigned long long* sel, uint64_t cap, Rec* dst, uint64_t out_stride, uint32_t n_obj,
-                            hipStream_t st);
-// dst[0..1] = (*sel > cap ? alt : src)[0..1]
+// a fast-path sweep's per-launch control words zeroed (kbound: set to no bound)
 hipError_t launch_zero_ctl(unsigned long long* counters, unsigned long long* qcount, unsigned int* wctr,
                            unsigned long long* counters_alt, unsigned long long* kbound, hipStream_t st);
+// tseed[o] = the K-th least of smin[o * nsamp .. + nsamp) (FastArgs::smin), all-ones when nsamp < K
 hipError_t launch_seed(const uint64_t* smin, uint32_t nsamp, uint32_t n_obj, uint32_t K, uint64_t* tseed,
                        hipStream_t st);
+// dst[0..1] = (*sel > cap ? alt : src)[0..1]
 hipError_t launch_pick_counters(const unsigned long long* src, const unsigned long long* alt,
                                 const unsigned long long* sel, uint64_t cap, uint64_t* dst, hipStream_t st);
-
+// dst[0..1] = the sum over i < n of src[i * stride + off + 0..1]
 hipError_t launch_sum_counters(const uint64_t* src, uint32_t n, uint64_t stride, uint64_t off, uint64_t* dst,
                                hipStream_t st);
+
 // ---- leaderless latencies for several quorum sizes (bote_quorums.hip)
 struct LqArgs {
   const uint32_t* mat;  // latency << 4
@@ -292,6 +299,7 @@ struct ChainHostLevel {
 hipError_t chain_search(const ChainHostLevel* lv, uint32_t ns, int ft_metric, double min_dec, uint64_t max_out,
                         uint32_t* out_idx, double* out_score, uint64_t* out_total, hipStream_t st, int* too_many);
 
+// ---- the per-call Bote::* API (bote_kernels.hip)
 hipError_t launch_single(const SingleArgs& a, int mode, hipStream_t st);
 hipError_t launch_best_leader(const SingleArgs& a, const uint64_t* vals, double* stat, hipStream_t st);
 

@@ -4,7 +4,7 @@ The device path (DESIGN.md §4 "The list dump"): each group-kernel block keeps
 the K least (key, rank) records of its configs; at its dump it publishes its
 K-th key with an atomicMin (fantoch_amd/csrc/bote_group.hip, `a.kbound`) and
 writes only the records whose key is at or below the least K-th key seen so
-far, then a terminator; `merge_wide_kernel` (bote_kernels.hip) counts each
+far, then a terminator; `merge_wide_kernel` (bote_merge.hip) counts each
 list's prefix at or below the final bound, gathers the prefixes in windows of
 `room` records and keeps the K least with a sort per window.
 
@@ -24,6 +24,13 @@ alone left ~70 % of every list (the least of the blocks' K-th order
 statistics is a loose bound when the blocks sample the same distribution);
 `test_gathered_records_stay_near_k` models that realistic case and fails on a
 loose bound.
+
+`seed_kernel` (bote_merge.hip) selects the K-th least of the sample launch's
+minima with a radix select of its own (8-bit digits).  `seed_rows` are the key
+patterns it is checked on, on the device (tests/test_gpu_seed.py); here the
+same patterns show that `wide_select` with the early stop off computes the
+same key (the seed as one call of it was tried and dropped for
+its registers and time, not its result).
 """
 import random
 
@@ -327,6 +334,39 @@ def test_wide_select_finds_a_valid_bound(seed):
     assert sum(1 for v in vals if v < x) + left == need
     y = wide_select(vals, need)[0]
     assert sum(1 for v in vals if v <= y) >= need
+
+
+def seed_rows(nsamp, K, rng):
+    """8 rows of nsamp u64 keys, one per pattern the seed's select must handle."""
+    u64 = np.uint64
+    means = rng.integers(0, 2**21, nsamp, dtype=u64)  # sums of latencies
+    top_byte = (rng.integers(0, 256, nsamp, dtype=u64) << u64(56)) | u64(0x0034_5678_9ABC_DEF1)
+    full = rng.integers(0, 2**64, nsamp, dtype=u64)
+    if nsamp >= 2:  # a range of at least 2^63: the first pass has no prefix to match (wide_select's s_hi == 64)
+        full[0], full[-1] = 1, ONES - 1
+    equal = np.full(nsamp, 40000, u64)
+    ties = rng.choice(np.array([1000, 1001, 1003, 1010, 2**40], u64), nsamp)  # heavy ties at the K-th
+    # mostly slots without a key (fewer than K real keys for the larger K)
+    mostly_ones = np.where(rng.random(nsamp) < 0.7, u64(ONES), rng.integers(0, 2**21, nsamp, dtype=u64))
+    extremes = rng.choice(np.array([0, 1, 2**63, ONES - 1, ONES], u64), nsamp)
+    # distinct even keys 2^20 apart, then the (K+1)-th least = the K-th least | 1
+    low_bit = np.arange(nsamp, dtype=u64) * u64(2**20) + u64(24690)
+    if nsamp > K:
+        low_bit[K] = low_bit[K - 1] | u64(1)
+    rng.shuffle(low_bit)
+    return np.stack([means, top_byte, full, equal, ties, mostly_ones, extremes, low_bit])
+
+
+@pytest.mark.parametrize("K", [1, 2, 100, 128])
+@pytest.mark.parametrize("nsamp", [1, 2, 63, 64, 65, 99, 100, 101, 128, 1024, 1025, 3072, 4096])
+def test_wide_select_is_the_seed(nsamp, K):
+    """wide_select with the early stop off computes the seed: the K-th least
+    key of every pattern, with too few keys mapping to all-ones (no bound)."""
+    for row in seed_rows(nsamp, K, np.random.default_rng(1000 * nsamp + K)):
+        vals = [int(v) for v in row]
+        r = wide_select(vals, K, stop_early=False)
+        seed_key = ONES if r is None else r[0]
+        assert seed_key == (sorted(vals)[K - 1] if nsamp >= K else ONES)
 
 
 @pytest.mark.parametrize("blocks", [1, 8, 32, 49])
