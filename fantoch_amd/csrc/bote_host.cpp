@@ -5,8 +5,6 @@
 #include <algorithm>
 #include <cmath>
 
-#include "../../include/bote_hip.h"  // (the slot and objective constants: plain C)
-
 namespace bote {
 namespace host {
 
@@ -469,6 +467,172 @@ void unpack_result(const uint8_t* blk, uint32_t n_obj, uint32_t K, uint32_t kp, 
   const uint64_t* cnt = (const uint64_t*)(blk + (size_t)n_obj * kp * 16);
   if (out_valid) *out_valid = cnt[0];
   if (out_digest) *out_digest = cnt[1];
+}
+
+// ------------------------------------------------------ argument checks --
+static Status fail(int code, std::string msg) { return Status{code, std::move(msg)}; }
+static const Status OK{};
+
+Status check_regions(const uint32_t* ids, uint32_t n, uint32_t R, bool distinct, const char* what) {
+  if (n && !ids) return fail(BOTE_E_ARG, std::string(what) + " is null");
+  std::vector<uint8_t> seen(R, 0);
+  for (uint32_t i = 0; i < n; ++i) {
+    if (ids[i] >= R) return fail(BOTE_E_ARG, std::string(what) + ": region id out of range");
+    if (distinct && seen[ids[i]]++) return fail(BOTE_E_ARG, std::string(what) + ": duplicate region");
+  }
+  return OK;
+}
+
+uint32_t distinct_count(const uint32_t* ids, uint32_t n, uint32_t R) {
+  std::vector<uint8_t> seen(R, 0);
+  uint32_t c = 0;
+  for (uint32_t i = 0; i < n; ++i)
+    if (!seen[ids[i]]++) ++c;
+  return c;
+}
+
+Status check_configs(const uint32_t* configs, uint64_t ncfg, uint32_t n, uint32_t ns) {
+  for (uint64_t i = 0; i < ncfg; ++i) {
+    uint32_t seen[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // (ns <= 256: the header's precondition)
+    for (uint32_t j = 0; j < n; ++j) {
+      uint32_t x = configs[i * n + j];
+      if (x >= ns) return fail(BOTE_E_ARG, "config position out of range");
+      if (seen[x >> 5] & (1u << (x & 31))) return fail(BOTE_E_ARG, "duplicate position in config");
+      seen[x >> 5] |= 1u << (x & 31);
+    }
+  }
+  return OK;
+}
+
+Status check_rank_range(uint32_t ns, uint32_t n, uint64_t rank_begin, uint64_t ncfg) {
+  const uint64_t total = binom_u64(ns, n);
+  if (rank_begin > total || ncfg > total - rank_begin) return fail(BOTE_E_ARG, "rank range out of bounds");
+  return OK;
+}
+
+Status check_rank_span(uint32_t ns, uint32_t n, uint64_t rank_begin, uint64_t rank_end) {
+  if (rank_begin > rank_end || rank_end > binom_u64(ns, n)) return fail(BOTE_E_ARG, "rank range out of bounds");
+  return OK;
+}
+
+Status check_ft_metric(int ft_metric) {
+  if (ft_metric != BOTE_FT_F1 && ft_metric != BOTE_FT_F1F2) return fail(BOTE_E_ARG, "bad ft_metric");
+  return OK;
+}
+
+// check_search_args in its two halves (bote_eval_leaderless checks its quorum
+// sizes between them): the sizes, then the lists
+static Status check_sizes(uint32_t R, uint32_t ns, uint32_t nc, uint32_t n, uint32_t min_n) {
+  if (R == 0) return fail(BOTE_E_ARG, "planet is null");
+  if (min_n < 2) {
+    if (n < 1 || n > BOTE_MAX_N) return fail(BOTE_E_RANGE, "config size must be in [1, 16]");
+  } else {
+    if (n < 2) return fail(BOTE_E_QUORUM_GT_N, "config size must be >= 2 (FPaxos q = 2)");
+    if (n > BOTE_MAX_N) return fail(BOTE_E_RANGE, "config size above 16");
+  }
+  if (n > ns) return fail(BOTE_E_ARG, "config size larger than the server list");
+  if (nc > BOTE_MAX_CLIENTS) return fail(BOTE_E_RANGE, "more than 4096 clients");
+  return OK;
+}
+static Status check_lists(uint32_t R, const uint32_t* servers, uint32_t ns, const uint32_t* clients, uint32_t nc) {
+  if (Status s = check_regions(servers, ns, R, true, "servers"); s.code) return s;
+  return check_regions(clients, nc, R, false, "clients");
+}
+// configs, or the rank range without them
+static Status check_work(uint32_t ns, uint32_t n, const uint32_t* configs, uint64_t rank_begin, uint64_t ncfg) {
+  if (ncfg == 0) return OK;
+  return configs ? check_configs(configs, ncfg, n, ns) : check_rank_range(ns, n, rank_begin, ncfg);
+}
+
+Status check_search_args(uint32_t R, const uint32_t* servers, uint32_t ns, const uint32_t* clients, uint32_t nc,
+                         uint32_t n, uint32_t min_n) {
+  if (Status s = check_sizes(R, ns, nc, n, min_n); s.code) return s;
+  return check_lists(R, servers, ns, clients, nc);
+}
+
+static Status check_quorum(uint32_t q, const uint32_t* servers, uint32_t ns, uint32_t R) {
+  if (q == 0) return fail(BOTE_E_ARG, "quorum size 0");
+  if (q > distinct_count(servers, ns, R)) return fail(BOTE_E_QUORUM_GT_N, "quorum larger than the server set");
+  return OK;
+}
+
+Status check_single_args(uint32_t R, const uint32_t* servers, uint32_t ns, const uint32_t* clients, uint32_t nc,
+                         const uint32_t* froms, uint32_t nf, uint32_t q, uint32_t leader, int mode) {
+  if (Status s = check_regions(servers, ns, R, false, "servers"); s.code) return s;
+  if (Status s = check_regions(clients, nc, R, false, "clients"); s.code) return s;
+  if (Status s = check_regions(froms, nf, R, false, "froms"); s.code) return s;
+  if (mode == 2 && leader >= R) return fail(BOTE_E_ARG, "leader out of range");
+  return check_quorum(q, servers, ns, R);
+}
+
+Status check_best_leader_args(uint32_t R, const uint32_t* servers, uint32_t ns, const uint32_t* clients, uint32_t nc,
+                              uint32_t q, int stat) {
+  if (ns == 0) return fail(BOTE_E_ARG, "the best leader should exist (empty server list)");
+  if (stat < 0 || stat > 2) return fail(BOTE_E_ARG, "unknown stat");
+  if (Status s = check_regions(servers, ns, R, false, "servers"); s.code) return s;
+  if (Status s = check_regions(clients, nc, R, false, "clients"); s.code) return s;
+  return check_quorum(q, servers, ns, R);
+}
+
+Status check_eval_args(uint32_t R, const uint32_t* servers, uint32_t ns, const uint32_t* clients, uint32_t nc,
+                       uint32_t n, const uint32_t* configs, uint64_t rank_begin, uint64_t ncfg,
+                       const bote_ranking_params* rp, uint32_t keys) {
+  if (keys > BOTE_KEYS_TEMPO_ALL_LEADERS) return fail(BOTE_E_ARG, "unknown key set");
+  if (Status s = check_search_args(R, servers, ns, clients, nc, n, 2); s.code) return s;
+  if (rp)
+    if (Status s = check_ft_metric(rp->ft_metric); s.code) return s;
+  return check_work(ns, n, configs, rank_begin, ncfg);
+}
+
+Status check_leaderless_args(uint32_t R, const uint32_t* servers, uint32_t ns, const uint32_t* clients, uint32_t nc,
+                             uint32_t n, const uint32_t* configs, uint64_t rank_begin, uint64_t ncfg,
+                             const uint32_t* quorum_sizes, uint32_t nq) {
+  if (Status s = check_sizes(R, ns, nc, n, 1); s.code) return s;
+  if (nq == 0 || nq > 8 || !quorum_sizes) return fail(BOTE_E_ARG, "1 to 8 quorum sizes");
+  for (uint32_t i = 0; i < nq; ++i) {
+    if (quorum_sizes[i] == 0) return fail(BOTE_E_ARG, "quorum size 0");
+    if (quorum_sizes[i] > n) return fail(BOTE_E_QUORUM_GT_N, "quorum larger than the config");
+  }
+  if (Status s = check_lists(R, servers, ns, clients, nc); s.code) return s;
+  return check_work(ns, n, configs, rank_begin, ncfg);
+}
+
+Status check_sweep_args(uint32_t R, const uint32_t* servers, uint32_t ns, const uint32_t* clients, uint32_t nc,
+                        uint32_t n, const bote_objective* objs, uint32_t n_obj, uint32_t K,
+                        const bote_ranking_params* rp, int kernel, uint32_t keys, bool& has_score) {
+  has_score = false;
+  if (keys > BOTE_KEYS_TEMPO_ALL_LEADERS) return fail(BOTE_E_ARG, "unknown key set");
+  if (kernel < BOTE_KERNEL_AUTO || kernel > BOTE_KERNEL_GROUP) return fail(BOTE_E_ARG, "unknown kernel path");
+  if (Status s = check_search_args(R, servers, ns, clients, nc, n, 2); s.code) return s;
+  if (n_obj > BOTE_MAX_OBJECTIVES) return fail(BOTE_E_RANGE, "more than 8 objectives");
+  if (n_obj && !objs) return fail(BOTE_E_ARG, "objectives null");
+  if (K == 0 || K > BOTE_MAX_K) return fail(BOTE_E_RANGE, "K must be in [1, 128]");
+  for (uint32_t o = 0; o < n_obj; ++o) {
+    if (objs[o].kind > BOTE_OBJ_COV) return fail(BOTE_E_ARG, "unknown objective kind");
+    if (objs[o].kind == BOTE_OBJ_SCORE) {
+      has_score = true;
+      continue;
+    }
+    if (objs[o].slot >= (keys ? BOTE_NSLOTS_X : BOTE_NSLOTS)) return fail(BOTE_E_ARG, "slot out of range");
+    if (!slot_exists_n(n, objs[o].slot, keys)) return fail(BOTE_E_ARG, "slot does not exist for this n (max_f < 2)");
+  }
+  if (has_score && !rp) return fail(BOTE_E_ARG, "SCORE objective needs ranking params");
+  if (rp) return check_ft_metric(rp->ft_metric);
+  return OK;
+}
+
+Status check_chain_levels(uint32_t ns, const uint32_t* counts, const uint64_t* const* masks,
+                          const double* const* scores, const double* const* means) {
+  for (int l = 0; l < 6; ++l) {
+    const uint32_t n = 3 + 2 * l;
+    if (counts[l] && (!masks[l] || !scores[l] || !means[l])) return fail(BOTE_E_ARG, "null level array");
+    for (uint32_t i = 0; i < counts[l]; ++i) {
+      const uint64_t m = masks[l][i];
+      if ((uint32_t)__builtin_popcountll(m) != n || (ns < 64 && (m >> ns)))
+        return fail(BOTE_E_ARG, "level mask is not an n-subset of the server list");
+    }
+  }
+  return OK;
 }
 
 }  // namespace host

@@ -3,8 +3,8 @@
 // chunks and shard splits, the client-quad layouts, the fast-path eligibility
 // test, the sweep planning (the exactness limits and flush counts of the fast
 // kernels, the score bands, the compiled-in objective set, the chunk states
-// and the top-K seed's sample plan) and the result-block unpacking.  Compiled
-// by g++ into the library and,
+// and the top-K seed's sample plan), the result-block unpacking and the
+// argument checks of the C ABI.  Compiled by g++ into the library and,
 // separately, under ASan/UBSan by tests/test_sanitize.py (tests/native/
 // host_check.cpp), so the driver's host code runs under the sanitizers the
 // oracle does.
@@ -12,7 +12,10 @@
 #include <cstddef>
 #include <cstdint>
 #include <memory>
+#include <string>
 #include <vector>
+
+#include "../../include/bote_hip.h"  // (codes, limits, bote_objective, bote_ranking_params: plain C)
 
 namespace bote {
 namespace host {
@@ -93,7 +96,7 @@ bool fast_eligible(const uint16_t* lat, uint32_t R, const uint32_t* servers, uin
                    bool fairness_threshold);
 
 // ------------------------------------------------------ sweep planning ---
-// The integer arithmetic of bote_sweep_create_keys (bote_capi.hip): which
+// The integer arithmetic of bote_sweep_create_keys (bote_capi_sweep.hip): which
 // kernel variants are exact for a planet and client count, and how often
 // their narrow accumulators flush.  The C ABI copies these into FastArgs.
 struct FastLimits {
@@ -160,6 +163,56 @@ struct TopkRecord {
 };
 void unpack_result(const uint8_t* blk, uint32_t n_obj, uint32_t K, uint32_t kp, TopkRecord* out, uint32_t* out_count,
                    uint64_t* out_valid, uint64_t* out_digest);
+
+// ------------------------------------------------------ argument checks --
+// What the C ABI (bote_capi*.hip) refuses before it touches a device: a
+// BOTE_E_* code and the text bote_last_error() then returns.  Each function
+// applies its checks in a fixed order and reports the first that fails; the
+// per-entry functions are the whole sequence of one entry point after its
+// null-handle test.  They take the planet's region count R, not the handle;
+// R == 0 stands for a null planet ("planet is null").
+struct Status {
+  int code = BOTE_OK;
+  std::string msg;
+};
+// `n` region ids below R (null only when n == 0), optionally pairwise distinct.
+Status check_regions(const uint32_t* ids, uint32_t n, uint32_t R, bool distinct, const char* what);
+// Distinct ids among `n` checked ones.
+uint32_t distinct_count(const uint32_t* ids, uint32_t n, uint32_t R);
+// ncfg explicit configs of n positions: each below ns, none twice in a config.
+// Needs ns <= 256 (the entries check the server list first: ns <= R <= 128).
+Status check_configs(const uint32_t* configs, uint64_t ncfg, uint32_t n, uint32_t ns);
+// [rank_begin, rank_begin + ncfg) inside the C(ns, n) ranks.
+Status check_rank_range(uint32_t ns, uint32_t n, uint64_t rank_begin, uint64_t ncfg);
+// rank_begin <= rank_end <= C(ns, n).
+Status check_rank_span(uint32_t ns, uint32_t n, uint64_t rank_begin, uint64_t rank_end);
+Status check_ft_metric(int ft_metric);
+// A search over n-subsets of the server list: the planet, min_n <= n <= 16
+// (min_n = 2: FPaxos needs q = 2; 1: leaderless quorums only; no other value
+// is meant: it picks between the two entries' texts), n <= ns, nc <= 4096,
+// then distinct servers and clients below R.
+Status check_search_args(uint32_t R, const uint32_t* servers, uint32_t ns, const uint32_t* clients, uint32_t nc,
+                         uint32_t n, uint32_t min_n);
+// bote_quorum_latencies .. bote_all_leaders (mode: bote::launch_single's; 2 reads `leader`).
+Status check_single_args(uint32_t R, const uint32_t* servers, uint32_t ns, const uint32_t* clients, uint32_t nc,
+                         const uint32_t* froms, uint32_t nf, uint32_t q, uint32_t leader, int mode);
+Status check_best_leader_args(uint32_t R, const uint32_t* servers, uint32_t ns, const uint32_t* clients, uint32_t nc,
+                              uint32_t q, int stat);
+// bote_eval and bote_eval_keys (configs null: the rank range).
+Status check_eval_args(uint32_t R, const uint32_t* servers, uint32_t ns, const uint32_t* clients, uint32_t nc,
+                       uint32_t n, const uint32_t* configs, uint64_t rank_begin, uint64_t ncfg,
+                       const bote_ranking_params* rp, uint32_t keys);
+Status check_leaderless_args(uint32_t R, const uint32_t* servers, uint32_t ns, const uint32_t* clients, uint32_t nc,
+                             uint32_t n, const uint32_t* configs, uint64_t rank_begin, uint64_t ncfg,
+                             const uint32_t* quorum_sizes, uint32_t nq);
+// bote_sweep_create_keys; has_score: some objective is BOTE_OBJ_SCORE.
+Status check_sweep_args(uint32_t R, const uint32_t* servers, uint32_t ns, const uint32_t* clients, uint32_t nc,
+                        uint32_t n, const bote_objective* objs, uint32_t n_obj, uint32_t K,
+                        const bote_ranking_params* rp, int kernel, uint32_t keys, bool& has_score);
+// bote_evolving_chains' six levels (n = 3, 5, .., 13): arrays present where a
+// level has entries, every mask an n-subset of the ns servers.
+Status check_chain_levels(uint32_t ns, const uint32_t* counts, const uint64_t* const* masks,
+                          const double* const* scores, const double* const* means);
 
 }  // namespace host
 }  // namespace bote

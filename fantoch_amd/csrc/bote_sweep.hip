@@ -1,6 +1,6 @@
 // bote_sweep.hip — the fast-path sweep kernel (gfx950): exhaustive search over
 // colex ranks with a block top-K, for planets that meet the fast-path
-// preconditions checked on the host (bote_capi.hip, fast_eligible):
+// preconditions checked on the host (bote_capi_sweep.hip, fast_eligible):
 //   * every latency <= 4095 (packed u16 keys: latency << 4 | member)
 //   * the server set is "simple": self latency 0, latency between two servers
 //     > 0 (a colocated client's nearest server is itself)

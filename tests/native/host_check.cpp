@@ -4,7 +4,8 @@
 // its chunk/shard cuts, quad layouts, the low table, fast-path eligibility,
 // the sweep planning (fast_limits, score_bands, the compiled-in objective set,
 // slot_exists_n, chunk_states, the seed's sample plan, sweep_runlen) and
-// result-block unpacking, each against a direct restatement.  Prints
+// result-block unpacking, each against a direct restatement, and the C ABI's
+// argument checks against their codes, texts and order.  Prints
 // "host ok" on success; any failed check exits 1.
 #include <algorithm>
 #include <chrono>
@@ -248,7 +249,7 @@ static void check_unpack() {
   unpack_result(blk.data(), n_obj, K, kp, nullptr, nullptr, nullptr, nullptr);  // all outputs optional
 }
 
-// The group geometry choice (bote_capi.hip): client-line coverage up to 8
+// The group geometry choice (bote_capi_sweep.hip): client-line coverage up to 8
 // per wave first, then waves per CU, then more lines, then the smaller size;
 // checked on the three measured R=128/R=64 cases.
 static void check_geometry() {
@@ -505,6 +506,10 @@ static void check_sample_plan() {
   CHECK(sample_count(1000, 1000 + 4096ull * 512, total, 4096, 100) == 4096);
   CHECK(sample_count(1000, 1000 + 4096ull * 512 - 1, total, 4096, 100) == 0);
   CHECK(sample_count(0, 0, total, 4096, 100) == 0 && sample_count(0, 63, total, 4096, 1) == 0);
+  // a rank space of C(16, 4) = 1,820 never samples, whatever the grid (>= 4 waves: one workgroup) and K
+  for (uint32_t nwaves = 4; nwaves <= 8192; ++nwaves)
+    for (uint32_t K : {1u, 4u, 128u})
+      CHECK(sample_count(0, 1820, 1820, nwaves, K) == 0 && sample_count(97, 97 + 67, 1820, nwaves, K) == 0);
   std::mt19937_64 rng(31);
   for (int i = 0; i < 2000; ++i) {
     const uint64_t tot = i % 2 ? total : binom_u64(128, 6);
@@ -528,7 +533,249 @@ static void check_sample_plan() {
   }
 }
 
+// ------------------------------------------------------ argument checks --
+// Every message of the C ABI's argument checks with its code, an accepted
+// input next to each boundary, and for the longer entry sequences an input
+// that breaks two checks (the earlier one's message must win).
+#define REFUSED(expr, want_code, want_msg)                                                              \
+  do {                                                                                                  \
+    const Status s_ = (expr);                                                                           \
+    if (s_.code != (want_code) || s_.msg != (want_msg)) {                                               \
+      std::printf("FAIL %s:%d: %s -> %d \"%s\"\n", __FILE__, __LINE__, #expr, s_.code, s_.msg.c_str()); \
+      ++failures;                                                                                       \
+    }                                                                                                   \
+  } while (0)
+#define ACCEPTED(expr) REFUSED(expr, BOTE_OK, "")
+
+static void check_arguments() {
+  std::vector<uint32_t> ids(4097);  // 0, 1, .., 127, 0, 1, ..: region ids of R = 128
+  for (size_t i = 0; i < ids.size(); ++i) ids[i] = (uint32_t)(i % 128);
+  const uint32_t* id = ids.data();
+
+  // region lists: R = 1 and 128, ids R - 1 and R, duplicates, null lists
+  {
+    const uint32_t zero[] = {0}, one[] = {1}, top[] = {5, 127}, over[] = {5, 128}, dup[] = {3, 9, 3};
+    ACCEPTED(check_regions(zero, 1, 1, true, "servers"));
+    REFUSED(check_regions(one, 1, 1, true, "servers"), BOTE_E_ARG, "servers: region id out of range");
+    ACCEPTED(check_regions(top, 2, 128, true, "clients"));
+    REFUSED(check_regions(over, 2, 128, false, "clients"), BOTE_E_ARG, "clients: region id out of range");
+    ACCEPTED(check_regions(id, 128, 128, true, "servers"));
+    REFUSED(check_regions(dup, 3, 128, true, "servers"), BOTE_E_ARG, "servers: duplicate region");
+    ACCEPTED(check_regions(dup, 3, 128, false, "froms"));
+    ACCEPTED(check_regions(nullptr, 0, 128, true, "froms"));
+    REFUSED(check_regions(nullptr, 1, 128, false, "froms"), BOTE_E_ARG, "froms is null");
+    CHECK(distinct_count(dup, 3, 128) == 2 && distinct_count(id, 300, 128) == 128 && distinct_count(nullptr, 0, 1) == 0);
+  }
+  // explicit configs: a position ns, a position twice; the second config is read too
+  {
+    const uint32_t good[] = {0, 1, 7, 7, 3, 5}, pos_ns[] = {0, 1, 7, 0, 1, 8}, twice[] = {2, 5, 2};
+    const uint32_t wide[] = {31, 32, 63, 64, 96, 127};  // every word of the position set
+    ACCEPTED(check_configs(good, 2, 3, 8));
+    REFUSED(check_configs(pos_ns, 2, 3, 8), BOTE_E_ARG, "config position out of range");
+    ACCEPTED(check_configs(pos_ns, 1, 3, 8));
+    REFUSED(check_configs(twice, 1, 3, 8), BOTE_E_ARG, "duplicate position in config");
+    ACCEPTED(check_configs(wide, 1, 6, 128));
+    ACCEPTED(check_configs(nullptr, 0, 3, 8));
+  }
+  // rank ranges of C(8, 4) = 70 ranks: begin + count and [begin, end] forms
+  {
+    const char* oob = "rank range out of bounds";
+    const struct { uint64_t rb, cnt; bool ok; } ranges[] = {
+        {0, 70, true}, {70, 0, true}, {69, 1, true}, {71, 0, false}, {0, 71, false}, {69, 2, false}, {1, ~0ull, false}};
+    for (auto& r : ranges) REFUSED(check_rank_range(8, 4, r.rb, r.cnt), r.ok ? BOTE_OK : BOTE_E_ARG, r.ok ? "" : oob);
+    const struct { uint64_t rb, re; bool ok; } spans[] = {
+        {0, 70, true}, {70, 70, true}, {0, 0, true}, {5, 4, false}, {0, 71, false}, {71, 71, false}};
+    for (auto& r : spans) REFUSED(check_rank_span(8, 4, r.rb, r.re), r.ok ? BOTE_OK : BOTE_E_ARG, r.ok ? "" : oob);
+  }
+  for (int ft = 0; ft <= 3; ++ft)
+    REFUSED(check_ft_metric(ft), ft == 1 || ft == 2 ? BOTE_OK : BOTE_E_ARG, ft == 1 || ft == 2 ? "" : "bad ft_metric");
+
+  // search arguments over R = 128: n = 1, 2, 16, 17; n = ns and ns + 1; 4096 and 4097 clients
+  {
+    const char *small = "config size must be >= 2 (FPaxos q = 2)", *big = "config size above 16",
+               *range1 = "config size must be in [1, 16]", *gt = "config size larger than the server list",
+               *clients = "more than 4096 clients";
+    const struct { uint32_t R, ns, nc, n, min_n; int code; const char* msg; } t[] = {
+        {128, 20, 20, 2, 2, BOTE_OK, ""},          {128, 20, 20, 1, 2, BOTE_E_QUORUM_GT_N, small},
+        {128, 20, 20, 16, 2, BOTE_OK, ""},         {128, 20, 20, 17, 2, BOTE_E_RANGE, big},
+        {128, 20, 20, 1, 1, BOTE_OK, ""},          {128, 20, 20, 0, 1, BOTE_E_RANGE, range1},
+        {128, 20, 20, 16, 1, BOTE_OK, ""},         {128, 20, 20, 17, 1, BOTE_E_RANGE, range1},
+        {128, 7, 20, 7, 2, BOTE_OK, ""},           {128, 7, 20, 8, 2, BOTE_E_ARG, gt},
+        {128, 20, 4096, 5, 2, BOTE_OK, ""},        {128, 20, 4097, 5, 2, BOTE_E_RANGE, clients},
+        {0, 20, 20, 5, 2, BOTE_E_ARG, "planet is null"}, {1, 1, 0, 1, 1, BOTE_OK, ""},
+        {128, 0, 0, 0, 2, BOTE_E_QUORUM_GT_N, small},  // (the size wins over the empty list)
+        {20, 20, 20, 5, 2, BOTE_OK, ""},           {19, 20, 20, 5, 2, BOTE_E_ARG, "servers: region id out of range"},
+        {19, 19, 20, 5, 2, BOTE_E_ARG, "clients: region id out of range"}};
+    for (auto& c : t) REFUSED(check_search_args(c.R, id, c.ns, id, c.nc, c.n, c.min_n), c.code, c.msg);
+    const uint32_t dup[] = {4, 6, 4, 9};
+    REFUSED(check_search_args(128, dup, 4, id, 20, 3, 2), BOTE_E_ARG, "servers: duplicate region");
+    ACCEPTED(check_search_args(128, id, 20, dup, 4, 3, 2));  // (clients may repeat)
+    REFUSED(check_search_args(128, nullptr, 4, id, 20, 3, 2), BOTE_E_ARG, "servers is null");
+  }
+  // the single-configuration entries (R = 8)
+  {
+    const uint32_t srv[] = {1, 1, 2}, bad[] = {1, 8, 2};
+    const char* gt = "quorum larger than the server set";
+    ACCEPTED(check_single_args(8, srv, 3, id, 8, id, 2, 2, 0, 1));  // (2 distinct servers)
+    REFUSED(check_single_args(8, srv, 3, id, 8, id, 2, 3, 0, 1), BOTE_E_QUORUM_GT_N, gt);
+    REFUSED(check_single_args(8, srv, 3, id, 8, nullptr, 0, 0, 0, 1), BOTE_E_ARG, "quorum size 0");
+    REFUSED(check_single_args(8, nullptr, 0, id, 8, nullptr, 0, 1, 0, 1), BOTE_E_QUORUM_GT_N, gt);
+    REFUSED(check_single_args(8, bad, 3, id, 8, nullptr, 0, 1, 0, 1), BOTE_E_ARG, "servers: region id out of range");
+    REFUSED(check_single_args(8, srv, 3, bad, 3, nullptr, 0, 1, 0, 1), BOTE_E_ARG, "clients: region id out of range");
+    REFUSED(check_single_args(8, srv, 3, id, 8, bad, 3, 1, 0, 0), BOTE_E_ARG, "froms: region id out of range");
+    REFUSED(check_single_args(8, srv, 3, id, 8, nullptr, 2, 1, 0, 0), BOTE_E_ARG, "froms is null");
+    ACCEPTED(check_single_args(8, srv, 3, id, 8, nullptr, 0, 1, 7, 2));
+    REFUSED(check_single_args(8, srv, 3, id, 8, nullptr, 0, 1, 8, 2), BOTE_E_ARG, "leader out of range");
+    ACCEPTED(check_single_args(8, srv, 3, id, 8, nullptr, 0, 1, 8, 3));  // (only bote_leader reads it)
+    // precedence: the lists, the leader, the quorum
+    REFUSED(check_single_args(8, bad, 3, bad, 3, nullptr, 0, 0, 8, 2), BOTE_E_ARG, "servers: region id out of range");
+    REFUSED(check_single_args(8, srv, 3, id, 8, bad, 3, 0, 8, 2), BOTE_E_ARG, "froms: region id out of range");
+    REFUSED(check_single_args(8, srv, 3, id, 8, nullptr, 0, 0, 8, 2), BOTE_E_ARG, "leader out of range");
+
+    const char* none = "the best leader should exist (empty server list)";
+    ACCEPTED(check_best_leader_args(8, srv, 3, id, 8, 2, 0));
+    ACCEPTED(check_best_leader_args(8, srv, 3, id, 8, 2, 2));
+    REFUSED(check_best_leader_args(8, srv, 3, id, 8, 2, 3), BOTE_E_ARG, "unknown stat");
+    REFUSED(check_best_leader_args(8, srv, 3, id, 8, 2, -1), BOTE_E_ARG, "unknown stat");
+    REFUSED(check_best_leader_args(8, srv, 0, id, 8, 2, 0), BOTE_E_ARG, none);
+    REFUSED(check_best_leader_args(8, srv, 3, id, 8, 0, 0), BOTE_E_ARG, "quorum size 0");
+    REFUSED(check_best_leader_args(8, srv, 3, id, 8, 3, 0), BOTE_E_QUORUM_GT_N, gt);
+    REFUSED(check_best_leader_args(8, srv, 3, bad, 3, 2, 0), BOTE_E_ARG, "clients: region id out of range");
+    // precedence: the empty list, the stat, the lists, the quorum
+    REFUSED(check_best_leader_args(8, bad, 0, id, 8, 0, 9), BOTE_E_ARG, none);
+    REFUSED(check_best_leader_args(8, bad, 3, id, 8, 0, 9), BOTE_E_ARG, "unknown stat");
+    REFUSED(check_best_leader_args(8, bad, 3, id, 8, 0, 1), BOTE_E_ARG, "servers: region id out of range");
+  }
+  // bote_eval / bote_eval_keys and bote_eval_leaderless: 8 servers, n = 4
+  {
+    bote_ranking_params rp{110.0, 35.0, 0.0, 15.0, BOTE_FT_F1F2};
+    const uint32_t cfg[] = {0, 1, 2, 7}, pos_ns[] = {0, 1, 2, 8}, twice[] = {0, 1, 1, 7};
+    const char *oob = "rank range out of bounds", *ft = "bad ft_metric";
+    ACCEPTED(check_eval_args(8, id, 8, id, 8, 4, nullptr, 0, 70, &rp, 0));
+    ACCEPTED(check_eval_args(8, id, 8, id, 8, 4, nullptr, 70, 0, nullptr, 1));  // [C, C]
+    ACCEPTED(check_eval_args(8, id, 8, id, 8, 4, nullptr, 71, 0, nullptr, 0));  // (no configs: the entry returns first)
+    REFUSED(check_eval_args(8, id, 8, id, 8, 4, nullptr, 71, 1, nullptr, 0), BOTE_E_ARG, oob);
+    REFUSED(check_eval_args(8, id, 8, id, 8, 4, nullptr, 0, 71, nullptr, 0), BOTE_E_ARG, oob);
+    REFUSED(check_eval_args(8, id, 8, id, 8, 4, nullptr, 0, 70, nullptr, 2), BOTE_E_ARG, "unknown key set");
+    ACCEPTED(check_eval_args(8, id, 8, id, 8, 4, cfg, 0, 1, &rp, 0));
+    REFUSED(check_eval_args(8, id, 8, id, 8, 4, pos_ns, 0, 1, &rp, 0), BOTE_E_ARG, "config position out of range");
+    REFUSED(check_eval_args(8, id, 8, id, 8, 4, twice, 0, 1, &rp, 0), BOTE_E_ARG, "duplicate position in config");
+    ACCEPTED(check_eval_args(8, id, 8, id, 8, 4, pos_ns, 0, 0, &rp, 0));  // (no configs: nothing is read)
+    for (int m : {0, 3}) {
+      rp.ft_metric = m;
+      REFUSED(check_eval_args(8, id, 8, id, 8, 4, cfg, 0, 1, &rp, 0), BOTE_E_ARG, ft);
+      // precedence: key set, planet, sizes, lists, ft_metric, work
+      REFUSED(check_eval_args(8, id, 8, id, 8, 4, pos_ns, 0, 1, &rp, 0), BOTE_E_ARG, ft);
+      REFUSED(check_eval_args(8, id, 8, id, 8, 4, nullptr, 71, 1, &rp, 0), BOTE_E_ARG, ft);
+      REFUSED(check_eval_args(8, id, 8, id, 9, 4, cfg, 0, 1, &rp, 0), BOTE_E_ARG, "clients: region id out of range");
+    }
+    REFUSED(check_eval_args(0, id, 8, id, 8, 4, cfg, 0, 1, &rp, 2), BOTE_E_ARG, "unknown key set");
+    REFUSED(check_eval_args(0, id, 8, id, 8, 1, cfg, 0, 1, &rp, 0), BOTE_E_ARG, "planet is null");
+    REFUSED(check_eval_args(8, id, 9, id, 8, 1, cfg, 0, 1, &rp, 0), BOTE_E_QUORUM_GT_N,
+            "config size must be >= 2 (FPaxos q = 2)");
+
+    const uint32_t qs[] = {1, 2, 3, 4, 4, 3, 2, 1, 1}, q0[] = {2, 0}, q5[] = {4, 5};
+    const char* count = "1 to 8 quorum sizes";
+    ACCEPTED(check_leaderless_args(8, id, 8, id, 8, 4, nullptr, 0, 70, qs, 8));
+    ACCEPTED(check_leaderless_args(8, id, 8, id, 8, 1, nullptr, 0, 8, qs, 1));  // n = 1
+    REFUSED(check_leaderless_args(8, id, 8, id, 8, 0, nullptr, 0, 1, qs, 1), BOTE_E_RANGE, "config size must be in [1, 16]");
+    REFUSED(check_leaderless_args(8, id, 8, id, 8, 4, nullptr, 0, 70, qs, 9), BOTE_E_ARG, count);
+    REFUSED(check_leaderless_args(8, id, 8, id, 8, 4, nullptr, 0, 70, qs, 0), BOTE_E_ARG, count);
+    REFUSED(check_leaderless_args(8, id, 8, id, 8, 4, nullptr, 0, 70, nullptr, 2), BOTE_E_ARG, count);
+    REFUSED(check_leaderless_args(8, id, 8, id, 8, 4, nullptr, 0, 70, q0, 2), BOTE_E_ARG, "quorum size 0");
+    REFUSED(check_leaderless_args(8, id, 8, id, 8, 4, nullptr, 0, 70, q5, 2), BOTE_E_QUORUM_GT_N, "quorum larger than the config");
+    REFUSED(check_leaderless_args(8, id, 8, id, 8, 4, nullptr, 1, 70, qs, 2), BOTE_E_ARG, oob);
+    REFUSED(check_leaderless_args(8, id, 8, id, 8, 4, twice, 0, 1, qs, 2), BOTE_E_ARG, "duplicate position in config");
+    ACCEPTED(check_leaderless_args(8, id, 8, id, 8, 4, cfg, 0, 1, qs, 2));
+    // precedence: planet, sizes, quorum sizes, lists, work
+    REFUSED(check_leaderless_args(0, id, 8, id, 8, 0, cfg, 0, 1, qs, 0), BOTE_E_ARG, "planet is null");
+    REFUSED(check_leaderless_args(8, id, 8, id, 4097, 4, cfg, 0, 1, qs, 0), BOTE_E_RANGE, "more than 4096 clients");
+    REFUSED(check_leaderless_args(8, id, 9, id, 8, 4, cfg, 0, 1, q5, 2), BOTE_E_QUORUM_GT_N, "quorum larger than the config");
+    REFUSED(check_leaderless_args(8, id, 9, id, 8, 4, pos_ns, 0, 1, qs, 2), BOTE_E_ARG, "servers: region id out of range");
+  }
+  // bote_sweep_create_keys (R = 8 = ns = nc)
+  {
+    const bote_ranking_params rp{110.0, 35.0, 0.0, 15.0, BOTE_FT_F1}, rp0{110.0, 35.0, 0.0, 15.0, 0},
+        rp3{110.0, 35.0, 0.0, 15.0, 3};
+    std::vector<bote_objective> mean(9, bote_objective{BOTE_OBJ_MEAN, BOTE_SLOT_E});
+    bool sc = true;
+    auto sweep = [&](uint32_t n, const bote_objective* o, uint32_t n_obj, uint32_t K, const bote_ranking_params* r,
+                     int kernel, uint32_t keys, uint32_t R = 8) {
+      return check_sweep_args(R, id, 8, id, 8, n, o, n_obj, K, r, kernel, keys, sc);
+    };
+    const char *kk = "K must be in [1, 128]", *slot = "slot out of range",
+               *f2 = "slot does not exist for this n (max_f < 2)", *need = "SCORE objective needs ranking params";
+    ACCEPTED(sweep(4, mean.data(), 8, 1, nullptr, BOTE_KERNEL_AUTO, 0));
+    CHECK(!sc);
+    ACCEPTED(sweep(4, mean.data(), 8, 128, &rp, BOTE_KERNEL_GROUP, 1));
+    ACCEPTED(sweep(4, nullptr, 0, 1, nullptr, BOTE_KERNEL_GENERIC, 0));
+    REFUSED(sweep(4, mean.data(), 9, 1, nullptr, 0, 0), BOTE_E_RANGE, "more than 8 objectives");
+    REFUSED(sweep(4, nullptr, 1, 1, nullptr, 0, 0), BOTE_E_ARG, "objectives null");
+    REFUSED(sweep(4, mean.data(), 1, 0, nullptr, 0, 0), BOTE_E_RANGE, kk);
+    REFUSED(sweep(4, mean.data(), 1, 129, nullptr, 0, 0), BOTE_E_RANGE, kk);
+    REFUSED(sweep(4, mean.data(), 1, 4, nullptr, 0, 2), BOTE_E_ARG, "unknown key set");
+    REFUSED(sweep(4, mean.data(), 1, 4, nullptr, -1, 0), BOTE_E_ARG, "unknown kernel path");
+    REFUSED(sweep(4, mean.data(), 1, 4, nullptr, 4, 0), BOTE_E_ARG, "unknown kernel path");
+    REFUSED(sweep(17, mean.data(), 1, 4, nullptr, 0, 0), BOTE_E_RANGE, "config size above 16");
+    const struct { uint32_t kind, slot, n, keys; int code; const char* msg; } objs[] = {
+        {BOTE_OBJ_COV, 9, 3, 0, BOTE_OK, ""},     {BOTE_OBJ_COV, 10, 3, 0, BOTE_E_ARG, slot},
+        {BOTE_OBJ_MEAN, 19, 4, 1, BOTE_OK, ""},   {BOTE_OBJ_MEAN, 20, 4, 1, BOTE_E_ARG, slot},
+        {BOTE_OBJ_MEAN, 10, 4, 1, BOTE_OK, ""},   {BOTE_OBJ_MEAN, BOTE_SLOT_AF2, 4, 0, BOTE_OK, ""},
+        {BOTE_OBJ_MEAN, BOTE_SLOT_AF2, 3, 0, BOTE_E_ARG, f2}, {BOTE_OBJ_MEAN, 19, 3, 1, BOTE_E_ARG, f2},
+        {3, 0, 4, 0, BOTE_E_ARG, "unknown objective kind"},  {BOTE_OBJ_SCORE, 99, 4, 0, BOTE_E_ARG, need}};
+    for (auto& c : objs) {
+      const bote_objective o[2] = {{BOTE_OBJ_MEAN, BOTE_SLOT_AF1}, {c.kind, c.slot}};
+      REFUSED(sweep(c.n, o, 2, 4, nullptr, 0, c.keys), c.code, c.msg);
+    }
+    const bote_objective score[2] = {{BOTE_OBJ_SCORE, 99}, {BOTE_OBJ_MEAN, 10}};  // (a SCORE slot is not read)
+    ACCEPTED(sweep(4, score, 1, 4, &rp, 0, 0));
+    CHECK(sc);
+    REFUSED(sweep(4, score, 1, 4, &rp0, 0, 0), BOTE_E_ARG, "bad ft_metric");
+    REFUSED(sweep(4, mean.data(), 1, 4, &rp3, 0, 0), BOTE_E_ARG, "bad ft_metric");  // (checked without SCORE too)
+    // precedence: key set, kernel, planet and lists, objective count, null, K, each objective, SCORE's params, ft_metric
+    REFUSED(sweep(4, nullptr, 9, 0, nullptr, 9, 2, 0), BOTE_E_ARG, "unknown key set");
+    REFUSED(sweep(4, nullptr, 9, 0, nullptr, 9, 1, 0), BOTE_E_ARG, "unknown kernel path");
+    REFUSED(sweep(4, nullptr, 9, 0, nullptr, 0, 0, 0), BOTE_E_ARG, "planet is null");
+    REFUSED(sweep(9, nullptr, 9, 0, nullptr, 0, 0), BOTE_E_ARG, "config size larger than the server list");
+    REFUSED(sweep(4, nullptr, 9, 0, nullptr, 0, 0), BOTE_E_RANGE, "more than 8 objectives");
+    REFUSED(sweep(4, nullptr, 2, 0, nullptr, 0, 0), BOTE_E_ARG, "objectives null");
+    REFUSED(sweep(4, score, 2, 0, nullptr, 0, 0), BOTE_E_RANGE, kk);
+    REFUSED(sweep(4, score, 2, 4, nullptr, 0, 0), BOTE_E_ARG, slot);
+    REFUSED(sweep(4, score, 1, 4, nullptr, 0, 0), BOTE_E_ARG, need);
+    REFUSED(sweep(4, score, 2, 4, &rp0, 0, 1), BOTE_E_ARG, "bad ft_metric");
+  }
+  // bote_evolving_chains' levels: n = 3, 5, ..: the popcount, a bit at ns
+  {
+    const double x[2] = {0, 0};
+    const char* bad = "level mask is not an n-subset of the server list";
+    auto chain = [&](uint32_t ns, uint32_t level, uint64_t m0, uint64_t m1, bool arrays = true) {
+      uint32_t counts[6] = {0, 0, 0, 0, 0, 0};
+      const uint64_t m[2] = {m0, m1};
+      const uint64_t* masks[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+      const double *sc[6] = {x, x, x, x, x, x}, *mn[6] = {x, x, x, x, x, x};
+      counts[level] = 2;
+      if (arrays) masks[level] = m;
+      return check_chain_levels(ns, counts, masks, sc, mn);
+    };
+    ACCEPTED(chain(5, 0, 0b00111, 0b11100));
+    REFUSED(chain(5, 0, 0b00111, 0b01100), BOTE_E_ARG, bad);   // 2 bits at n = 3
+    REFUSED(chain(5, 0, 0b00111, 0b11110), BOTE_E_ARG, bad);   // 4 bits
+    REFUSED(chain(5, 0, 0b100011, 0b00111), BOTE_E_ARG, bad);  // 3 bits, one at position ns
+    ACCEPTED(chain(6, 0, 0b100011, 0b00111));
+    ACCEPTED(chain(5, 1, 0b11111, 0b11111));
+    REFUSED(chain(5, 1, 0b00111, 0b11111), BOTE_E_ARG, bad);  // n = 5 at level 1
+    ACCEPTED(chain(64, 0, 7ull << 61, 0b111));  // (ns = 64: no position is past the mask)
+    REFUSED(chain(63, 0, 7ull << 61, 0b111), BOTE_E_ARG, bad);
+    REFUSED(chain(5, 2, 0, 0, false), BOTE_E_ARG, "null level array");
+    uint32_t none[6] = {0, 0, 0, 0, 0, 0};
+    const uint64_t* nomask[6] = {};
+    const double* nod[6] = {};
+    ACCEPTED(check_chain_levels(5, none, nomask, nod, nod));  // (empty levels need no arrays)
+  }
+}
+
 int main() {
+  check_arguments();
   check_fast_limits();
   check_score_bands();
   check_objective_sets();

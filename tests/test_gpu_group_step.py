@@ -21,7 +21,7 @@ from fantoch_amd.planet import Planet
 
 pytestmark = pytest.mark.gpu
 
-# client-line slots a wave gets at most (bote_capi.hip group_geometry)
+# client-line slots a wave gets at most (bote_capi_sweep.hip group_geometry)
 MAX_LINE_SLOTS = 16
 
 

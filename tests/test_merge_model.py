@@ -267,7 +267,7 @@ def test_bound_is_no_tighter_than_the_union_kth_key():
 
 @pytest.mark.parametrize("seed", range(6))
 def test_per_wave_sample_minima_bound_the_kth_key(seed):
-    """The top-K seed (bote_capi.hip sample_seed, FastArgs::smin_wave): each
+    """The top-K seed (bote_capi_sweep.hip sample_seed, FastArgs::smin_wave): each
     wave's slot is the least key over the chunks it took, and the seed is the
     K-th least slot (all-ones when fewer than K slots hold a key).  K slots at
     or below the seed are K distinct configs of the range, so the seed is an
