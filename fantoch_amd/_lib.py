@@ -33,6 +33,7 @@ SLOT_X_COLOCATED = 4
 NSLOTS_X = 20
 SLOT_NAMES_X = SLOT_NAMES + ["ttf1", "ttf2", "twf1", "twf2", "ttf1C", "ttf2C", "twf1C", "twf2C", "fl1", "fl2"]
 OBJ_SCORE, OBJ_MEAN, OBJ_COV = 0, 1, 2
+OBJ_MAX = 16  # the slot's worst client, then its sum: key = max << 32 | sum (bote.max_key)
 FT_F1, FT_F1F2 = 1, 2
 KP = 128
 

@@ -698,6 +698,13 @@ CONFIG5_OBJECTIVES = DEFAULT_OBJECTIVES + [(_lib.OBJ_MEAN, _lib.SLOT_TT1), (_lib
                                            (_lib.OBJ_MEAN, _lib.SLOT_FL1)]
 
 
+def max_key(key: int) -> Tuple[int, int]:
+    """(max, sum) of an OBJ_MAX record's key: the slot's Histogram::max
+    (histogram.rs:102-108) in the high 32 bits, its exact sum (the OBJ_MEAN
+    key) in the low 32."""
+    return int(key) >> 32, int(key) & 0xFFFFFFFF
+
+
 @dataclass
 class SweepResult:
     tops: List[List[Tuple[int, int]]]  # per objective: (key, rank) ascending

@@ -18,7 +18,7 @@ main.rs:31-60).  Subcommands expose them, and the sweep the hot path serves:
   python -m fantoch_amd distance-table [--lat-dir D] [--regions a,b,...]
   python -m fantoch_amd stats --config a,b,c [--clients ...] [--tempo] [--lat-dir D]
   python -m fantoch_amd sweep (--synthetic R [--seed S] | --lat-dir D) --n N [--K 100]
-                        [--objectives default|config5|mean:af1,cov:af1,score,...]
+                        [--objectives default|config5|mean:af1,cov:af1,max:af1,score,...]
                         [--keys base|tempo-all-leaders] [--gpus G] [--rank-begin B --rank-end E]
 """
 from __future__ import annotations
@@ -117,7 +117,7 @@ def _objectives(spec: str):
         return list(DEFAULT_OBJECTIVES)
     if spec == "config5":
         return list(CONFIG5_OBJECTIVES)
-    kinds = {"score": _lib.OBJ_SCORE, "mean": _lib.OBJ_MEAN, "cov": _lib.OBJ_COV}
+    kinds = {"score": _lib.OBJ_SCORE, "mean": _lib.OBJ_MEAN, "cov": _lib.OBJ_COV, "max": _lib.OBJ_MAX}
     out = []
     for item in spec.split(","):
         if item == "score":
@@ -136,7 +136,7 @@ def sweep(args, out=sys.stdout) -> dict:
     import numpy as np
 
     from . import _lib
-    from .bote import DEFAULT_RANKING, DevicePlanet, MultiDeviceSearch, Sweep
+    from .bote import DEFAULT_RANKING, DevicePlanet, MultiDeviceSearch, Sweep, max_key
 
     planet = _planet(args)
     srv = np.arange(planet.R, dtype=np.uint32)
@@ -160,12 +160,18 @@ def sweep(args, out=sys.stdout) -> dict:
     def regions(rank):
         return [planet.names[i] for i in _lib.colex_unrank(int(rank), args.n, planet.R)]
 
-    names = {_lib.OBJ_SCORE: "score", _lib.OBJ_MEAN: "mean", _lib.OBJ_COV: "cov"}
+    names = {_lib.OBJ_SCORE: "score", _lib.OBJ_MEAN: "mean", _lib.OBJ_COV: "cov", _lib.OBJ_MAX: "max"}
+
+    def record(kind, key, rank):
+        rec = {"key": str(key), "rank": rank, "regions": regions(rank)}
+        if kind == _lib.OBJ_MAX:  # the composite key's halves
+            rec["max"], rec["sum"] = max_key(key)
+        return rec
+
     doc = {"regions": planet.R, "n": args.n, "rank_begin": rb, "rank_end": re, "configs": re - rb,
            "keys": args.keys, "gpus": args.gpus, "valid": res.valid, "digest": str(res.digest),
            "objectives": [{"objective": names[k] + ("" if k == _lib.OBJ_SCORE else ":" + _lib.SLOT_NAMES_X[s]),
-                           "top": [{"key": str(key), "rank": rank, "regions": regions(rank)}
-                                   for key, rank in res.tops[o][:args.show]]}
+                           "top": [record(k, key, rank) for key, rank in res.tops[o][:args.show]]}
                           for o, (k, s) in enumerate(objs)]}
     print(json.dumps(doc, indent=None if args.compact else 1), file=out)
     return doc

@@ -156,7 +156,9 @@ static int sweep_plan_group(bote_sweep* s, const FastLimits& lim, bool compiled_
   const bote_planet* p = s->p;
   const uint32_t n = s->n, ns = s->ns, nc = s->nc;
   bote::FastArgs& f = s->fargs;
-  bool want_group = n >= 4 && ns <= 256 && group_utilisation(ns, n) >= 0.9;
+  // (a MAX objective: the fast kernel's TAIL variant; a forced group kernel
+  // was refused with the arguments, check_sweep_args)
+  bool want_group = n >= 4 && ns <= 256 && group_utilisation(ns, n) >= 0.9 && !s->tail;
   if (kernel != BOTE_KERNEL_AUTO) want_group = n >= 4 && ns <= 256 && kernel == BOTE_KERNEL_GROUP;
   if (kernel == BOTE_KERNEL_GROUP && !want_group) return fail(BOTE_E_ARG, "group kernel needs n >= 4");
   if (s->path == Path::Generic || !want_group) return BOTE_OK;
@@ -278,6 +280,10 @@ static int sweep_plan_fast(bote_sweep* s, const uint32_t* servers, const uint32_
   // objective set, compiled into it, and moments that fit its 32-bit
   // arithmetic: FastLimits::keys32) or on the generic kernel
   const bool compiled_objs = is_compiled_objective_set(a.obj_kind, a.obj_slot, s->n_obj, keys);
+  // a MAX objective: the TAIL variant of the fast kernel (base key set), else
+  // the generic kernel
+  s->tail = false;
+  for (uint32_t o = 0; o < s->n_obj; ++o) s->tail = s->tail || a.obj_kind[o] == BOTE_OBJ_MAX;
   const FastLimits lim = fast_limits(p->lat.data(), p->R, nc, n);
   if (keys && eligible &&
       (!bote::group_supports_keys(n, bote::GROUP_XK_MAX_BD) || !compiled_objs || !lim.keys32 ||
@@ -305,11 +311,11 @@ static int sweep_plan_fast(bote_sweep* s, const uint32_t* servers, const uint32_
   const char* abl = getenv("BOTE_ABLATE");  // timing-diagnostics builds only
   f.ablate = abl ? (uint32_t)strtoul(abl, nullptr, 0) : 0u;
 #endif
-  s->fshm = bote::fast_smem_bytes(f, n);
+  s->fshm = bote::fast_smem_bytes(f, n, s->tail);
   if (s->fshm > device_max_lds(p->device)) {
     s->path = Path::Generic;
   } else {
-    s->fgrid = (uint32_t)(device_cus(p->device) * bote::fast_occupancy(n, s->fshm));
+    s->fgrid = (uint32_t)(device_cus(p->device) * bote::fast_occupancy(n, s->tail, s->fshm));
   }
   if ((rc = sweep_plan_group(s, lim, compiled_objs, kernel))) return rc;
   // the fast (non-group) kernel does not compute the extended key set
@@ -630,7 +636,7 @@ static int launch_fast_path(bote_sweep* s, uint64_t rb, uint64_t re, hipStream_t
   s->last0 = *e0;
   s->last1 = *e1;
   if (group) HIP_TRY(bote::launch_group(f, s->n, s->def_obj, s->fgrid, s->fshm, st, *e0, *e1));
-  else HIP_TRY(bote::launch_fast(f, s->n, s->fgrid, s->fshm, st, *e0, *e1));
+  else HIP_TRY(bote::launch_fast(f, s->n, s->tail, s->fgrid, s->fshm, st, *e0, *e1));
   // exact fixup of the deferred configs: generic kernel over the rank list
   EvalArgs a = s->args;
   a.rank_list = s->queue.as<uint64_t>();

@@ -290,6 +290,10 @@ __device__ __forceinline__ uint64_t cov_key(const Mom& m) {
   return (uint64_t)__double_as_longlong(rr);
 }
 
+// MAX objective key (BOTE_OBJ_MAX): the slot's largest value, then its exact
+// sum (max <= 2 * 16383 and S1 < 2^27: include/bote_hip.h).
+__device__ __forceinline__ uint64_t max_key(uint32_t mx, uint64_t s1) { return ((uint64_t)mx << 32) | s1; }
+
 // Per-config digest, summed over configs mod 2^64.  A linear
 // fold of 32-bit words, each times its own constant as two 16-bit halves (one
 // v_dot2_u32_u16 per word, in any order), then the rank and the leader, then

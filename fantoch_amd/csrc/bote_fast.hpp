@@ -26,8 +26,11 @@ __device__ __forceinline__ void defer_rank(const FastArgs& a, uint64_t rank) {
 // is shift invariant, so it is also V of ff1 and ff2).  `thr` holds the
 // block's current K-th record per objective (only .key is read).  Returns
 // false when a COV decision is within the ambiguity band: the caller defers
-// the config and offers nothing to the top-K.
-template <int N>
+// the config and offers nothing to the top-K.  TAIL (the fast kernel's
+// worst-client variant): a MAX objective's key and ok are left as the caller,
+// which holds the slots' maxima, set them; without it no objective has that
+// kind.
+template <int N, bool TAIL = false>
 __device__ __forceinline__ bool finish_config(const FastArgs& a, const Mom (&mom)[NSLOT], double vcol_lead,
                                               uint32_t lead_member, uint64_t rank, const Rec* thr, double pnc1,
                                               double pnc2, uint64_t& valid_cnt, uint64_t& digest,
@@ -123,6 +126,7 @@ __device__ __forceinline__ bool finish_config(const FastArgs& a, const Mom (&mom
       }
       continue;
     }
+    if (TAIL && kind == OBJ_MAX) continue;
 #pragma unroll
     for (int q = 0; q < NSLOT; ++q) {
       if ((uint32_t)q != sl) continue;

@@ -607,15 +607,20 @@ Status check_sweep_args(uint32_t R, const uint32_t* servers, uint32_t ns, const 
   if (n_obj > BOTE_MAX_OBJECTIVES) return fail(BOTE_E_RANGE, "more than 8 objectives");
   if (n_obj && !objs) return fail(BOTE_E_ARG, "objectives null");
   if (K == 0 || K > BOTE_MAX_K) return fail(BOTE_E_RANGE, "K must be in [1, 128]");
+  bool has_max = false;
   for (uint32_t o = 0; o < n_obj; ++o) {
-    if (objs[o].kind > BOTE_OBJ_COV) return fail(BOTE_E_ARG, "unknown objective kind");
+    if (objs[o].kind > BOTE_OBJ_COV && objs[o].kind != BOTE_OBJ_MAX) return fail(BOTE_E_ARG, "unknown objective kind");
     if (objs[o].kind == BOTE_OBJ_SCORE) {
       has_score = true;
       continue;
     }
     if (objs[o].slot >= (keys ? BOTE_NSLOTS_X : BOTE_NSLOTS)) return fail(BOTE_E_ARG, "slot out of range");
     if (!slot_exists_n(n, objs[o].slot, keys)) return fail(BOTE_E_ARG, "slot does not exist for this n (max_f < 2)");
+    has_max = has_max || objs[o].kind == BOTE_OBJ_MAX;
   }
+  // (after the objectives: a bad kind or slot is reported whatever the path)
+  if (has_max && kernel == BOTE_KERNEL_GROUP)
+    return fail(BOTE_E_ARG, "the group kernel does not compute MAX objectives (fast or generic kernel)");
   if (has_score && !rp) return fail(BOTE_E_ARG, "SCORE objective needs ranking params");
   if (rp) return check_ft_metric(rp->ft_metric);
   return OK;

@@ -205,7 +205,11 @@ Status check_eval_args(uint32_t R, const uint32_t* servers, uint32_t ns, const u
 Status check_leaderless_args(uint32_t R, const uint32_t* servers, uint32_t ns, const uint32_t* clients, uint32_t nc,
                              uint32_t n, const uint32_t* configs, uint64_t rank_begin, uint64_t ncfg,
                              const uint32_t* quorum_sizes, uint32_t nq);
-// bote_sweep_create_keys; has_score: some objective is BOTE_OBJ_SCORE.
+// bote_sweep_create_keys; has_score: some objective is BOTE_OBJ_SCORE.  In
+// order: the key set, the kernel path, check_search_args, the objective
+// count, a null list, K, then per objective its kind, slot range and slot
+// existence for n; then a MAX objective on a forced group kernel (which does
+// not compute it), SCORE without ranking params, and the ft_metric.
 Status check_sweep_args(uint32_t R, const uint32_t* servers, uint32_t ns, const uint32_t* clients, uint32_t nc,
                         uint32_t n, const bote_objective* objs, uint32_t n_obj, uint32_t K,
                         const bote_ranking_params* rp, int kernel, uint32_t keys, bool& has_score);

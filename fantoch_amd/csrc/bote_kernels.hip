@@ -31,6 +31,7 @@ struct Smem {
   uint32_t* clioff;  // nc    client row offsets (cli[c] * R)
   uint32_t* srv;     // ns    server region ids
   uint64_t* cs;      // 2*ns  per position: sum_c L[c][srv[p]], sum_c L^2
+  uint32_t* cmx;     // ns    per position: max_c L[c][srv[p]] (the MAX keys of FPaxos)
   uint64_t* binom;   // (ns+1)*(N+1)
   uint32_t* qtab;    // N * BD * NLW
   TopkLds tk;        // top MAXOBJ*KP, cand BD, tmp KP, thr MAXOBJ, cnt
@@ -56,12 +57,13 @@ __host__ __device__ inline size_t smem_layout(const EvalArgs& a, int N, int NLW,
   off[8] = o; o += topk ? (size_t)KP * 16 : 0;
   off[9] = o; o += topk ? (size_t)MAXOBJ * 16 : 0;
   off[10] = o; o += 48;
+  off[11] = o; o += (size_t)a.ns * 4;  // cmx
   return o;
 }
 
 template <int N>
 __device__ inline Smem carve(const EvalArgs& a, unsigned char* base, int NLW) {
-  size_t off[11];
+  size_t off[12];
   smem_layout(a, N, NLW, blockDim.x, a.out_top != nullptr, off);
   Smem s;
   s.mat = (uint32_t*)(base + off[0]);
@@ -75,6 +77,7 @@ __device__ inline Smem carve(const EvalArgs& a, unsigned char* base, int NLW) {
   s.tk.tmp = (Rec*)(base + off[8]);
   s.tk.thr = (Rec*)(base + off[9]);
   s.tk.cnt = (int*)(base + off[10]);
+  s.cmx = (uint32_t*)(base + off[11]);
   return s;
 }
 
@@ -95,6 +98,7 @@ template <int N, bool X>
 struct CfgOut {
   static constexpr int NS = X ? NSLOT_X : NSLOT;
   Mom mom[NS];
+  uint32_t mx[NS];  // Histogram::max per slot (top-K sweeps only: the MAX keys)
   Mom al[X ? 2 : 1][X ? N : 1];
   uint32_t lead_orig;
   double score;
@@ -226,20 +230,30 @@ __device__ __forceinline__ void eval_config(const EvalArgs& a, const Smem& s, co
     out.mom[SLOT_FF1] = leader_mom(c1, c2, nc, q);
     q = lq2;
     out.mom[SLOT_FF2] = leader_mom(c1, c2, nc, q);
+    if (!FULL) {  // the worst client of the leader's column, plus the quorum latency
+      const uint32_t cm = s.cmx[lpos];
+      out.mx[SLOT_FF1] = cm + lq1;
+      out.mx[SLOT_FF2] = cm + lq2;
+    }
   }
 
   // --- Colocated keys: clients are the config members (config order).
   {
     uint64_t f1 = 0, f1s = 0, f2 = 0, f2s = 0;
     uint64_t l1[NL], l2[NL];
+    uint32_t fm = 0, lm[NL];
 #pragma unroll
-    for (int t = 0; t < NL; ++t) l1[t] = l2[t] = 0;
+    for (int t = 0; t < NL; ++t) {
+      l1[t] = l2[t] = 0;
+      lm[t] = 0;
+    }
 #pragma unroll
     for (int k = 0; k < N; ++k) {
       uint32_t v = s.mat[moff[k] + lreg] >> LAT_SHIFT;  // ping_latency(client k, leader)
       uint32_t x1 = v + lq1, x2 = v + lq2;
       f1 += x1; f1s += (uint64_t)x1 * x1;
       f2 += x2; f2s += (uint64_t)x2 * x2;
+      fm = max(fm, v);
       uint32_t d = cdk[k] >> LAT_SHIFT, js = cdk[k] & 15;
       uint32_t A[NL];
 #pragma unroll
@@ -247,6 +261,7 @@ __device__ __forceinline__ void eval_config(const EvalArgs& a, const Smem& s, co
         A[t] = d + sel(Ql[t], js);
         l1[t] += A[t];
         l2[t] += (uint64_t)A[t] * A[t];
+        lm[t] = max(lm[t], A[t]);
       }
       if (wv) {
         uint32_t* oc = ov + 5 * nc;
@@ -270,6 +285,20 @@ __device__ __forceinline__ void eval_config(const EvalArgs& a, const Smem& s, co
       out.mom[4 + SLOT_TT2] = Mom{l1[t4], l2[t4], (uint32_t)N};
       out.mom[4 + SLOT_TW2] = Mom{l1[t3], l2[t3], (uint32_t)N};
     }
+    if (!FULL) {
+      out.mx[5 + SLOT_FF1] = fm + lq1;
+      out.mx[5 + SLOT_FF2] = fm + lq2;
+      out.mx[5 + SLOT_AF1] = lm[QC::idx_a1];
+      out.mx[5 + SLOT_AF2] = lm[QC::idx_a2];
+      out.mx[5 + SLOT_E] = lm[QC::idx_e];
+      if constexpr (X) {
+        constexpr int t2 = QT::idx(2), t3 = QT::idx(3) < 0 ? 0 : QT::idx(3), t4 = QT::idx(4) < 0 ? 0 : QT::idx(4);
+        out.mx[4 + SLOT_TT1] = lm[t2];
+        out.mx[4 + SLOT_TW1] = lm[t2];
+        out.mx[4 + SLOT_TT2] = lm[t4];
+        out.mx[4 + SLOT_TW2] = lm[t3];
+      }
+    }
   }
 
   // --- Input leaderless: the hot loop.  Per client (wave-uniform): the
@@ -278,8 +307,9 @@ __device__ __forceinline__ void eval_config(const EvalArgs& a, const Smem& s, co
   {
     uint32_t S1[NL];
     uint64_t S2[NL];
+    uint32_t M[NL];
 #pragma unroll
-    for (int t = 0; t < NL; ++t) { S1[t] = 0; S2[t] = 0; }
+    for (int t = 0; t < NL; ++t) { S1[t] = 0; S2[t] = 0; M[t] = 0; }
     for (uint32_t c = 0; c < nc; ++c) {
       const uint32_t off = s.clioff[c];
       uint32_t m = 0xFFFFFFFFu;
@@ -297,6 +327,7 @@ __device__ __forceinline__ void eval_config(const EvalArgs& a, const Smem& s, co
       for (int t = 0; t < NL; ++t) {
         S1[t] += A[t];
         S2[t] += (uint64_t)A[t] * A[t];
+        if (!FULL) M[t] = max(M[t], A[t]);
       }
       if (wv) {
         uint32_t v = s.mat[off + lreg] >> LAT_SHIFT;
@@ -318,11 +349,24 @@ __device__ __forceinline__ void eval_config(const EvalArgs& a, const Smem& s, co
       out.mom[SLOT_TT2] = Mom{S1[t4], S2[t4], nc};
       out.mom[SLOT_TW2] = Mom{S1[t3], S2[t3], nc};
     }
+    if (!FULL) {
+      out.mx[SLOT_AF1] = M[QC::idx_a1];
+      out.mx[SLOT_AF2] = M[QC::idx_a2];
+      out.mx[SLOT_E] = M[QC::idx_e];
+      if constexpr (X) {
+        constexpr int t2 = QT::idx(2), t3 = QT::idx(3) < 0 ? 0 : QT::idx(3), t4 = QT::idx(4) < 0 ? 0 : QT::idx(4);
+        out.mx[SLOT_TT1] = M[t2];
+        out.mx[SLOT_TW1] = M[t2];
+        out.mx[SLOT_TT2] = M[t4];
+        out.mx[SLOT_TW2] = M[t3];
+      }
+    }
   }
   if constexpr (X) {
     // FPaxos all leaders (Bote::all_leaders_stats, lib.rs:129-150), Input
     // clients, q = f + 1, leaders in config order, and the best leader by
     // Stats::Mean (lib.rs:99-121: the first minimum, exact sums)
+    uint32_t alm[2][N] = {};  // the leaders' worst clients
 #pragma unroll
     for (int o = 0; o < N; ++o) {
       uint32_t l = 0;
@@ -333,15 +377,31 @@ __device__ __forceinline__ void eval_config(const EvalArgs& a, const Smem& s, co
       const uint64_t q1 = sel(Qf1, l), q2 = sel(Qf2, l);
       out.al[0][o] = leader_mom(c1, c2, nc, q1);
       out.al[1][o] = leader_mom(c1, c2, nc, q2);
+      if (!FULL) {
+        const uint32_t cm = s.cmx[pl];
+        alm[0][o] = cm + (uint32_t)q1;
+        alm[1][o] = cm + (uint32_t)q2;
+      }
     }
     Mom b1 = out.al[0][0], b2 = out.al[1][0];
+    uint32_t m1 = alm[0][0], m2 = alm[1][0];
 #pragma unroll
     for (int o = 1; o < N; ++o) {
-      if (out.al[0][o].s1 < b1.s1) b1 = out.al[0][o];
-      if (out.al[1][o].s1 < b2.s1) b2 = out.al[1][o];
+      if (out.al[0][o].s1 < b1.s1) {
+        b1 = out.al[0][o];
+        m1 = alm[0][o];
+      }
+      if (out.al[1][o].s1 < b2.s1) {
+        b2 = out.al[1][o];
+        m2 = alm[1][o];
+      }
     }
     out.mom[SLOT_FL1] = b1;
     out.mom[SLOT_FL2] = b2;
+    if (!FULL) {
+      out.mx[SLOT_FL1] = m1;
+      out.mx[SLOT_FL2] = m2;
+    }
   }
 
   // --- Search::compute_score (search.rs:421-472), bit-exact.
@@ -435,14 +495,17 @@ __global__ void __launch_bounds__(256) eval_kernel(EvalArgs a) {
   __syncthreads();
   for (uint32_t i = tid; i < a.ns; i += BD) {
     uint64_t c1 = 0, c2 = 0;
+    uint32_t cm = 0;
     const uint32_t col = s.srv[i];
     for (uint32_t c = 0; c < a.nc; ++c) {
       uint64_t v = s.mat[s.clioff[c] + col] >> LAT_SHIFT;
       c1 += v;
       c2 += v * v;
+      cm = max(cm, (uint32_t)v);
     }
     s.cs[2 * i] = c1;
     s.cs[2 * i + 1] = c2;
+    s.cmx[i] = cm;
   }
   __syncthreads();
 
@@ -545,7 +608,10 @@ __global__ void __launch_bounds__(256) eval_kernel(EvalArgs a) {
               // registers (a select chain here gets turned into scratch).
 #pragma unroll
               for (int q = 0; q < NS; ++q)
-                if ((uint32_t)q == sl) key[o] = kind == OBJ_MEAN ? r.mom[q].s1 : cov_key(r.mom[q]);
+                if ((uint32_t)q == sl)
+                  key[o] = kind == OBJ_MEAN  ? r.mom[q].s1
+                           : kind == OBJ_MAX ? max_key(r.mx[q], r.mom[q].s1)
+                                             : cov_key(r.mom[q]);
             }
           }
         }
@@ -661,7 +727,7 @@ __global__ void __launch_bounds__(256) best_leader_kernel(SingleArgs a, const ui
 
 // ------------------------------------------------------------- launchers --
 size_t eval_smem_bytes(const EvalArgs& a, uint32_t n, uint32_t bd, bool topk) {
-  size_t off[11];
+  size_t off[12];
   int nl = 0;
   const bool x = a.keys != 0;
   switch (n) {

@@ -8,7 +8,7 @@ namespace bote {
 constexpr int NSLOT = 10;
 constexpr int G_MERGE_LISTS = 8;  // lists merged per workgroup
 enum { SLOT_AF1 = 0, SLOT_FF1 = 1, SLOT_AF2 = 2, SLOT_FF2 = 3, SLOT_E = 4 };
-enum { OBJ_SCORE = 0, OBJ_MEAN = 1, OBJ_COV = 2 };
+enum { OBJ_SCORE = 0, OBJ_MEAN = 1, OBJ_COV = 2, OBJ_MAX = 16 };
 
 struct EvalArgs {
   // planet (device): latency << 4, row = from
@@ -208,11 +208,14 @@ struct FastArgs {
 #else
 #define ABLATE(a, bit) false
 #endif
-size_t fast_smem_bytes(const FastArgs& a, uint32_t n);
-int fast_occupancy(uint32_t n, size_t shm);
+// `tail`: the TAIL variant of the fast kernel, which also carries every
+// slot's maximum (the worst client) for BOTE_OBJ_MAX objectives; the plain
+// kernel treats no such objective
+size_t fast_smem_bytes(const FastArgs& a, uint32_t n, bool tail);
+int fast_occupancy(uint32_t n, bool tail, size_t shm);
 // (e0, e1: events carried by the dispatch itself, bote_launch.hpp, for a timed launch)
-hipError_t launch_fast(const FastArgs& a, uint32_t n, uint32_t grid, size_t shm, hipStream_t st, hipEvent_t e0 = nullptr,
-                       hipEvent_t e1 = nullptr);
+hipError_t launch_fast(const FastArgs& a, uint32_t n, bool tail, uint32_t grid, size_t shm, hipStream_t st,
+                       hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
 size_t group_smem_bytes(const FastArgs& a, uint32_t n);
 bool group_uses_lines(uint32_t n);  // n <= 7: client lines (FastArgs::gslots) and register lookups
 // the extended key set's group kernels target BOTE_GROUP_WAVES_XK waves per

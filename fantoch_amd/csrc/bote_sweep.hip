@@ -41,10 +41,11 @@ struct FastSmem {
   uint64_t* cs2;
   double* vcol;
   uint64_t* binom;
+  uint32_t* cmax;  // TAIL: per position, the largest client latency of its column
   TopkLds tk;
 };
 
-__host__ __device__ inline size_t fast_layout(const FastArgs& a, int N, int NLW, size_t* off) {
+__host__ __device__ inline size_t fast_layout(const FastArgs& a, int N, int NLW, bool tail, size_t* off) {
   size_t o = 0;
   off[0] = o; o += (size_t)N * FAST_BD * NLW * 4;  // qtab first: offsets stay small
   off[1] = o; o += (size_t)a.R * a.cq_stride * 8;
@@ -61,11 +62,12 @@ __host__ __device__ inline size_t fast_layout(const FastArgs& a, int N, int NLW,
   off[10] = o; o += (size_t)KP * 16;          // tmp
   off[11] = o; o += (size_t)MAXOBJ * 16;      // thr
   off[12] = o; o += 48;                       // cnt[1 + MAXOBJ]
+  off[13] = o; o += tail ? (size_t)a.ns * 4 : 0;  // cmax
   return o;
 }
 
-size_t fast_smem_bytes(const FastArgs& a, uint32_t n) {
-  size_t off[13];
+size_t fast_smem_bytes(const FastArgs& a, uint32_t n, bool tail) {
+  size_t off[14];
   int nl = 0;
   switch (n) {
 #define NL_CASE(NN) case NN: nl = QCfg<NN>::NL; break;
@@ -74,7 +76,7 @@ size_t fast_smem_bytes(const FastArgs& a, uint32_t n) {
 #undef NL_CASE
     default: return 0;
   }
-  return fast_layout(a, (int)n, nl <= 2 ? 1 : 2, off);
+  return fast_layout(a, (int)n, nl <= 2 ? 1 : 2, tail, off);
 }
 
 template <int N>
@@ -93,18 +95,23 @@ __device__ __forceinline__ uint32_t sel_u(const uint32_t (&arr)[N], uint32_t i) 
 // one qtab read for the nearest member's quorum latencies; packed adds and
 // v_dot2_u32_u16 accumulate the sum and the sum of squares.  Squares are
 // accumulated in 32 bits and flushed to 64 bits every `flushQ` quads.
-template <int N, int NL>
+// TAIL: also each table's largest client latency into MX, one packed max
+// (v_pk_max_u16) per half quad into a running register per table, taken after
+// the remainder mask (a dead client counts 0); no LDS traffic is added.
+template <int N, int NL, bool TAIL>
 __device__ __forceinline__ void client_quads(const unsigned char* B, uint32_t cqt, uint32_t nq, uint32_t rem,
                                              uint32_t flushQ, const uint32_t (&colT)[N], uint32_t qlane,
-                                             uint32_t (&S1)[NL], uint64_t (&S2)[NL]) {
+                                             uint32_t (&S1)[NL], uint64_t (&S2)[NL], uint32_t (&MX)[NL]) {
   const us2 ones = {1, 1};
   constexpr int NQ = NL == 3 ? 8 : 4;  // qtab words per quad
   uint32_t s2[NL];
+  us2 pm[NL];  // TAIL: running packed maxima
 #pragma unroll
   for (int t = 0; t < NL; ++t) {
     S1[t] = 0;
     S2[t] = 0;
     s2[t] = 0;
+    if constexpr (TAIL) pm[t] = us2{0, 0};
   }
   uint32_t col[N];
 #pragma unroll
@@ -152,6 +159,7 @@ __device__ __forceinline__ void client_quads(const unsigned char* B, uint32_t cq
     S1[t] = __builtin_amdgcn_udot2(a23, ones, S1[t], false);
     s2[t] = __builtin_amdgcn_udot2(a01, a01, s2[t], false);
     s2[t] = __builtin_amdgcn_udot2(a23, a23, s2[t], false);
+    if constexpr (TAIL) pm[t] = __builtin_elementwise_max(__builtin_elementwise_max(pm[t], a01), a23);
   };
   auto accum = [&](us2 lo, us2 hi, const uint32_t (&q)[NQ], uint32_t mlo, uint32_t mhi) {
     const us2 dlo = lo >> (us2)4, dhi = hi >> (us2)4;
@@ -227,18 +235,31 @@ __device__ __forceinline__ void client_quads(const unsigned char* B, uint32_t cq
     quad(nq * 8, mlo, mhi);
     flush();
   }
+  if constexpr (TAIL) {
+#pragma unroll
+    for (int t = 0; t < NL; ++t) MX[t] = max((uint32_t)pm[t].x, (uint32_t)pm[t].y);
+  }
 }
 
 // ---------------------------------------------------------- the kernel ----
-template <int N>
+// TAIL: the variant for sweeps with a MAX objective (base key set).  It also
+// carries each slot's maximum: the Input leaderless tables' from the client
+// loop, Input FPaxos in closed form (the leader column's largest latency,
+// staged per position beside cs1/cs2, plus the quorum latency), and the
+// colocated slots' from the values the Q phase and the N-step loop already
+// hold.  The MAX keys are built just before finish_config, which leaves them
+// alone, and withdrawn when it defers the config: built after it, the ten
+// maxima stay live across the score and digest arithmetic and N = 7 spills
+// (8 B/lane of scratch; none this way).
+template <int N, bool TAIL>
 __global__ void __launch_bounds__(FAST_BD, 4) sweep_fast_kernel(FastArgs a) {
   using QC = QCfg<N>;
   constexpr int NL = QC::NL;
   constexpr int NLW = NL <= 2 ? 1 : 2;
   constexpr int P = Pow2<N - 1>::v;  // off-diagonal row values, padded
   extern __shared__ __align__(16) unsigned char smem[];
-  size_t off[13];
-  fast_layout(a, N, NLW, off);
+  size_t off[14];
+  fast_layout(a, N, NLW, TAIL, off);
   FastSmem s;
   s.base = smem;
   s.qtab = (uint32_t)off[0];
@@ -249,6 +270,7 @@ __global__ void __launch_bounds__(FAST_BD, 4) sweep_fast_kernel(FastArgs a) {
   s.cs2 = (uint64_t*)(smem + off[5]);
   s.vcol = (double*)(smem + off[6]);
   s.binom = (uint64_t*)(smem + off[7]);
+  s.cmax = (uint32_t*)(smem + off[13]);
   s.tk.top = (Rec*)(smem + off[8]);
   s.tk.cand = (Rec*)(smem + off[9]);
   s.tk.tmp = (Rec*)(smem + off[10]);
@@ -279,11 +301,14 @@ __global__ void __launch_bounds__(FAST_BD, 4) sweep_fast_kernel(FastArgs a) {
   for (uint32_t i = tid; i < a.ns; i += FAST_BD) {
     const uint32_t col = s.cqt + s.srv[i] * cstride;
     uint64_t c1 = 0, c2 = 0;
+    uint32_t cm = 0;
     for (uint32_t c = 0; c < a.nc; ++c) {
       uint64_t v = ld16(B, col + (c >> 2) * 8 + (c & 3) * 2) >> LAT_SHIFT;
       c1 += v;
       c2 += v * v;
+      if constexpr (TAIL) cm = max(cm, (uint32_t)v);
     }
+    if constexpr (TAIL) s.cmax[i] = cm;
     s.cs1[i] = (uint32_t)c1;
     s.cs2[i] = c2;
     s.vcol[i] = (double)((uint64_t)a.nc * c2 - c1 * c1);  // exact: < 2^53
@@ -330,8 +355,9 @@ __global__ void __launch_bounds__(FAST_BD, 4) sweep_fast_kernel(FastArgs a) {
         // ---- Q phase: sorted off-diagonal distances of each member's row
         uint32_t Q2[N], Q3[N];
         uint32_t cS1[NL], cS2[NL];
+        uint32_t cMX[NL];  // TAIL: the colocated leaderless maxima
 #pragma unroll
-        for (int t = 0; t < NL; ++t) cS1[t] = cS2[t] = 0;
+        for (int t = 0; t < NL; ++t) cS1[t] = cS2[t] = cMX[t] = 0;
 #pragma unroll
         for (int j = 0; j < N; ++j) {
           uint32_t v[P];
@@ -357,6 +383,7 @@ __global__ void __launch_bounds__(FAST_BD, 4) sweep_fast_kernel(FastArgs a) {
             ql[t2] = v[QC::lq(t2) - 2];
             cS1[t2] += ql[t2];
             cS2[t2] += ql[t2] * ql[t2];
+            if constexpr (TAIL) cMX[t2] = max(cMX[t2], ql[t2]);
           }
           *(uint32_t*)(smem + qlane + ((uint32_t)j << QSH)) = ql[0] | (NL >= 2 ? ql[NL >= 2 ? 1 : 0] << 16 : 0u);
           if (NL == 3) *(uint32_t*)(smem + qlane + ((uint32_t)(N + j) << QSH)) = ql[NL - 1];
@@ -400,12 +427,14 @@ __global__ void __launch_bounds__(FAST_BD, 4) sweep_fast_kernel(FastArgs a) {
         }
         if (have) {
           Mom mom[NSLOT];
+          uint32_t mx[NSLOT];  // TAIL: the slots' maxima
           // Input leaderless: the hot loop (first, so little is live across it)
           {
             uint32_t S1[NL];
             uint64_t S2[NL];
-            client_quads<N, NL>(B, s.cqt, ABLATE(a, 1) ? 0u : nq, ABLATE(a, 1) ? 0u : rem, a.s2_flush, colT,
-                                qlane, S1, S2);
+            uint32_t MX[NL];
+            client_quads<N, NL, TAIL>(B, s.cqt, ABLATE(a, 1) ? 0u : nq, ABLATE(a, 1) ? 0u : rem, a.s2_flush, colT,
+                                      qlane, S1, S2, MX);
             if (ABLATE(a, 1)) {  // timing only: non-degenerate dummy sums (nothing defers)
 #pragma unroll
               for (int t = 0; t < NL; ++t) {
@@ -416,17 +445,29 @@ __global__ void __launch_bounds__(FAST_BD, 4) sweep_fast_kernel(FastArgs a) {
             mom[SLOT_AF1] = Mom{S1[QC::idx_a1], S2[QC::idx_a1], nc};
             mom[SLOT_AF2] = Mom{S1[QC::idx_a2], S2[QC::idx_a2], nc};
             mom[SLOT_E] = Mom{S1[QC::idx_e], S2[QC::idx_e], nc};
+            if constexpr (TAIL) {
+              mx[SLOT_AF1] = MX[QC::idx_a1];
+              mx[SLOT_AF2] = MX[QC::idx_a2];
+              mx[SLOT_E] = MX[QC::idx_e];
+            }
           }
           // Input FPaxos: moments from the leader column's sums
           mom[SLOT_FF1] = leader_mom(s.cs1[lp], s.cs2[lp], nc, lq2);
           mom[SLOT_FF2] = leader_mom(s.cs1[lp], s.cs2[lp], nc, lq3);
+          if constexpr (TAIL) {
+            const uint32_t cm = s.cmax[lp];
+            mx[SLOT_FF1] = cm + lq2;
+            mx[SLOT_FF2] = cm + lq3;
+          }
           // Colocated: leaderless values are the members' own quorum latencies;
           // FPaxos reads the leader's column of the config submatrix.
           {
             uint32_t f1 = 0, f1s = 0, f2 = 0, f2s = 0;
+            uint32_t fm = 0;  // TAIL: the members' largest latency to the leader
 #pragma unroll
             for (int k = 0; k < N; ++k) {
               const uint32_t v = ld16(B, lcol + rowq[k]) >> LAT_SHIFT;
+              if constexpr (TAIL) fm = max(fm, v);
               const uint32_t x1 = v + lq2, x2 = v + lq3;
               f1 += x1;
               f1s += x1 * x1;
@@ -438,10 +479,39 @@ __global__ void __launch_bounds__(FAST_BD, 4) sweep_fast_kernel(FastArgs a) {
             mom[5 + SLOT_AF1] = Mom{cS1[QC::idx_a1], cS2[QC::idx_a1], (uint32_t)N};
             mom[5 + SLOT_AF2] = Mom{cS1[QC::idx_a2], cS2[QC::idx_a2], (uint32_t)N};
             mom[5 + SLOT_E] = Mom{cS1[QC::idx_e], cS2[QC::idx_e], (uint32_t)N};
+            if constexpr (TAIL) {
+              mx[5 + SLOT_FF1] = fm + lq2;
+              mx[5 + SLOT_FF2] = fm + lq3;
+              mx[5 + SLOT_AF1] = cMX[QC::idx_a1];
+              mx[5 + SLOT_AF2] = cMX[QC::idx_a2];
+              mx[5 + SLOT_E] = cMX[QC::idx_e];
+            }
           }
-          if (!finish_config<N>(a, mom, s.vcol[lp], bi, rank, s.tk.thr, pnc1, pnc2, valid_cnt, digest, key, ok)) {
+          if constexpr (TAIL) {
+            // the MAX keys first (the maxima die here, before the score and
+            // digest arithmetic); a deferred config withdraws them below
+#pragma unroll
+            for (int o = 0; o < MAXOBJ; ++o) {
+              if (o >= a.n_obj) break;
+              if (a.obj_kind[o] != OBJ_MAX) continue;
+              const uint32_t sl = a.obj_slot[o];
+              // `sl` is uniform: one scalar branch per slot
+#pragma unroll
+              for (int q = 0; q < NSLOT; ++q) {
+                if ((uint32_t)q != sl) continue;
+                ok[o] = true;
+                key[o] = max_key(mx[q], mom[q].s1);
+              }
+            }
+          }
+          if (!finish_config<N, TAIL>(a, mom, s.vcol[lp], bi, rank, s.tk.thr, pnc1, pnc2, valid_cnt, digest, key,
+                                      ok)) {
             defer_rank(a, rank);
             have = false;
+            if constexpr (TAIL) {
+#pragma unroll
+              for (int o = 0; o < MAXOBJ; ++o) ok[o] = false;
+            }
           }
         }
       }
@@ -460,9 +530,10 @@ __global__ void __launch_bounds__(FAST_BD, 4) sweep_fast_kernel(FastArgs a) {
 // ------------------------------------------------------------- launcher ---
 // the kernel for config size n (null: unsupported), for the occupancy query
 // and the launch alike
-static const void* fast_fn(uint32_t n) {
+static const void* fast_fn(uint32_t n, bool tail) {
   switch (n) {
-#define FN_CASE(NN) case NN: return (const void*)sweep_fast_kernel<NN>;
+#define FN_CASE(NN) \
+  case NN: return tail ? (const void*)sweep_fast_kernel<NN, true> : (const void*)sweep_fast_kernel<NN, false>;
     FN_CASE(2) FN_CASE(3) FN_CASE(4) FN_CASE(5) FN_CASE(6) FN_CASE(7) FN_CASE(8) FN_CASE(9)
     FN_CASE(10) FN_CASE(11) FN_CASE(12) FN_CASE(13) FN_CASE(14) FN_CASE(15) FN_CASE(16)
 #undef FN_CASE
@@ -470,14 +541,14 @@ static const void* fast_fn(uint32_t n) {
   }
 }
 
-int fast_occupancy(uint32_t n, size_t shm) {
-  const void* k = fast_fn(n);
+int fast_occupancy(uint32_t n, bool tail, size_t shm) {
+  const void* k = fast_fn(n, tail);
   return k ? kernel_occupancy(k, FAST_BD, shm, 1) : 0;
 }
 
-hipError_t launch_fast(const FastArgs& a, uint32_t n, uint32_t grid, size_t shm, hipStream_t st, hipEvent_t e0,
-                       hipEvent_t e1) {
-  const void* k = fast_fn(n);
+hipError_t launch_fast(const FastArgs& a, uint32_t n, bool tail, uint32_t grid, size_t shm, hipStream_t st,
+                       hipEvent_t e0, hipEvent_t e1) {
+  const void* k = fast_fn(n, tail);
   return k ? launch_kernel(k, a, grid, FAST_BD, shm, st, e0, e1) : hipErrorInvalidValue;
 }
 

@@ -90,6 +90,9 @@ extern "C" {
 #define BOTE_OBJ_SCORE 0 /* max Search::compute_score among valid configs (search.rs:421-472) */
 #define BOTE_OBJ_MEAN 1  /* min Histogram::mean of `slot` (exact sum order)          */
 #define BOTE_OBJ_COV 2   /* min Histogram::cov of `slot`, keyed fl64(V / S1^2)        */
+/* min Histogram::max of `slot` (histogram.rs:102-108: the worst client), then
+ * min mean among the configs sharing it.  Kinds 3..15 are not defined. */
+#define BOTE_OBJ_MAX 16
 
 /* Sweep kernel paths (bote_sweep_create_ex); every path is exact. */
 #define BOTE_KERNEL_AUTO 0    /* group kernel when eligible, else fast, else generic */
@@ -123,6 +126,11 @@ typedef struct {
  *   MEAN:  key = exact integer sum of the histogram (count is fixed per slot)
  *   COV:   key = IEEE bits of fl64(V / S1^2), V = count*sum(x^2) - S1^2;
  *          ~0 when the reference's COV is NaN (count <= 1 or S1 == 0)
+ *   MAX:   key = (max << 32) | S1: the slot's largest value (over the Input
+ *          clients for slots 0..4 and the Input slots of the extended key set,
+ *          over the n members for the colocated slots), then its exact sum
+ *          (the MEAN key).  Both fit: a value is a latency plus a quorum
+ *          latency, max <= 2 * 16383, and S1 <= 4096 * 2 * 16383 < 2^27.
  * rank = colex rank of the config: rank = sum_j C(p_j, j+1), p ascending
  * positions into the server list. */
 typedef struct {
@@ -257,7 +265,10 @@ int bote_sweep_create(const bote_planet* p, const uint32_t* servers, uint32_t ns
                       const bote_objective* objs, uint32_t n_obj, uint32_t K,
                       const bote_ranking_params* rp, int digest, bote_sweep** out);
 /* bote_sweep_create with an explicit kernel path (BOTE_KERNEL_*); a forced
- * fast/group path that the planet or lists do not qualify for is BOTE_E_ARG. */
+ * fast/group path that the planet or lists do not qualify for is BOTE_E_ARG.
+ * A BOTE_OBJ_MAX objective runs on the fast kernel's worst-client variant
+ * (AUTO, base key set, eligible planet) or the generic kernel; the group
+ * kernel does not compute it, so a forced BOTE_KERNEL_GROUP is BOTE_E_ARG. */
 int bote_sweep_create_ex(const bote_planet* p, const uint32_t* servers, uint32_t ns,
                          const uint32_t* clients, uint32_t nc, uint32_t n,
                          const bote_objective* objs, uint32_t n_obj, uint32_t K,

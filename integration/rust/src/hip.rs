@@ -32,6 +32,8 @@ pub const BOTE_STAT_MDTM: c_int = 2;
 pub const BOTE_OBJ_SCORE: u32 = 0;
 pub const BOTE_OBJ_MEAN: u32 = 1;
 pub const BOTE_OBJ_COV: u32 = 2;
+/// min worst client of a slot, then min sum: key = (max << 32) | sum
+pub const BOTE_OBJ_MAX: u32 = 16;
 
 #[repr(C)]
 pub struct bote_planet {
