@@ -37,6 +37,18 @@ OBJ_MAX = 16  # the slot's worst client, then its sum: key = max << 32 | sum (bo
 FT_F1, FT_F1F2 = 1, 2
 KP = 128
 
+
+def OBJ_PCTL(bp: int) -> int:
+    """The objective kind of Histogram::percentile(bp / 10000.0), 1 <= bp <= 9999 (p95 = 9500):
+    key = (2 * percentile) << 32 | sum (bote.pctl_key), BOTE_OBJ_PCTL of include/bote_hip.h."""
+    if not 1 <= int(bp) <= 9999:
+        raise ValueError(f"percentile {bp} / 10000 is outside 0.0001 .. 0.9999")
+    return 0x10000 | int(bp)
+
+
+def is_pctl(kind: int) -> bool:
+    return (int(kind) >> 16) == 1 and 1 <= (int(kind) & 0xFFFF) <= 9999
+
 # Every symbol declared in include/bote_hip.h (checked by tests/test_abi.py).
 EXPORTS = [
     "bote_last_error", "bote_device_count", "bote_planet_create", "bote_planet_destroy",
@@ -47,7 +59,7 @@ EXPORTS = [
     "bote_sweep_destroy", "bote_colex_unrank", "bote_binomial", "bote_sweep_timing_reset",
     "bote_sweep_timing", "bote_sweep_grid", "bote_sweep_is_fast", "bote_sweep_split", "bote_sweep_create_ex", "bote_search_topk", "bote_sweep_deferred", "bote_eval_leaderless", "bote_evolving_chains",
     "bote_search_create", "bote_search_launch", "bote_search_result", "bote_search_bounds", "bote_search_destroy",
-    "bote_eval_keys", "bote_sweep_create_keys",
+    "bote_eval_keys", "bote_sweep_create_keys", "bote_percentile_index",
 ]
 KERNELS = {None: 0, "auto": 0, "generic": 1, "fast": 2, "group": 3}
 
@@ -162,6 +174,8 @@ def lib():
     L.bote_colex_unrank.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, _u32p]
     L.bote_binomial.restype = C.c_uint64
     L.bote_binomial.argtypes = [C.c_uint32, C.c_uint32]
+    if hasattr(L, "bote_percentile_index"):  # (absent from an older BOTE_LIB_PATH build loaded for A/B timing)
+        L.bote_percentile_index.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_int)]
     _LIB = L
     return L
 
@@ -193,6 +207,15 @@ def device_count() -> int:
 
 def binomial(ns: int, n: int) -> int:
     return int(lib().bote_binomial(ns, n))
+
+
+def percentile_index(bp: int, count: int):
+    """(idx, whole) of Histogram::percentile(bp / 10000.0) over `count` values (histogram.rs:110-170):
+    idx = round(p * count), whole = p * count is that integer.  With the values ascending as s, the
+    percentile is s[0] when idx == 0, (s[idx-1] + s[idx]) / 2 when whole, else s[idx-1]."""
+    idx, whole = C.c_uint32(0), C.c_int(0)
+    check(lib().bote_percentile_index(bp, count, C.byref(idx), C.byref(whole)))
+    return idx.value, bool(whole.value)
 
 
 def colex_unrank(rank: int, n: int, ns: int) -> np.ndarray:

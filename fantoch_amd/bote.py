@@ -705,6 +705,22 @@ def max_key(key: int) -> Tuple[int, int]:
     return int(key) >> 32, int(key) & 0xFFFFFFFF
 
 
+def pctl_key(key: int) -> Tuple[int, int]:
+    """(twice_percentile, sum) of an OBJ_PCTL record's key: 2 * Histogram::percentile
+    (histogram.rs:110-170; an exact integer, the percentile may be a midpoint) in the
+    high 32 bits, the slot's exact sum (the OBJ_MEAN key) in the low 32."""
+    return int(key) >> 32, int(key) & 0xFFFFFFFF
+
+
+def pctl_kind(p: float) -> int:
+    """The objective kind of percentile `p` (0.95 -> _lib.OBJ_PCTL(9500)); p must be
+    a multiple of 0.0001 in 0.0001 .. 0.9999."""
+    bp = round(float(p) * 10000)
+    if abs(float(p) * 10000 - bp) > 1e-6:
+        raise ValueError(f"percentile {p} is not a multiple of 0.0001")
+    return _lib.OBJ_PCTL(bp)
+
+
 @dataclass
 class SweepResult:
     tops: List[List[Tuple[int, int]]]  # per objective: (key, rank) ascending

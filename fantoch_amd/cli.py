@@ -18,7 +18,7 @@ main.rs:31-60).  Subcommands expose them, and the sweep the hot path serves:
   python -m fantoch_amd distance-table [--lat-dir D] [--regions a,b,...]
   python -m fantoch_amd stats --config a,b,c [--clients ...] [--tempo] [--lat-dir D]
   python -m fantoch_amd sweep (--synthetic R [--seed S] | --lat-dir D) --n N [--K 100]
-                        [--objectives default|config5|mean:af1,cov:af1,max:af1,score,...]
+                        [--objectives default|config5|mean:af1,cov:af1,max:af1,p95:af1,p99.9:e,score,...]
                         [--keys base|tempo-all-leaders] [--gpus G] [--rank-begin B --rank-end E]
 """
 from __future__ import annotations
@@ -109,6 +109,29 @@ def config_stats(args, out=sys.stdout) -> None:
             print(f"{key}={stats.map[key]!r}", file=out)
 
 
+def _pctl_kind(name: str):
+    """p95, p99.9, p99.99 -> the percentile objective kind (None: not of that form);
+    up to two decimals, 0.01 .. 99.99."""
+    import re
+
+    from . import _lib
+
+    m = re.fullmatch(r"p(\d{1,2})(?:\.(\d{1,2}))?", name)
+    if not m:
+        return None
+    bp = int(m.group(1)) * 100 + int((m.group(2) or "").ljust(2, "0"))
+    return _lib.OBJ_PCTL(bp)  # (p0 is refused there)
+
+
+def _objective_name(kind: int) -> str:
+    from . import _lib
+
+    if _lib.is_pctl(kind):
+        whole, frac = divmod(kind & 0xFFFF, 100)
+        return f"p{whole}" + (f".{frac:02d}".rstrip("0") if frac else "")
+    return {_lib.OBJ_SCORE: "score", _lib.OBJ_MEAN: "mean", _lib.OBJ_COV: "cov", _lib.OBJ_MAX: "max"}[kind]
+
+
 def _objectives(spec: str):
     from . import _lib
     from .bote import CONFIG5_OBJECTIVES, DEFAULT_OBJECTIVES
@@ -124,7 +147,8 @@ def _objectives(spec: str):
             out.append((_lib.OBJ_SCORE, 0))
             continue
         kind, slot = item.split(":")
-        out.append((kinds[kind], _lib.SLOT_NAMES_X.index(slot)))
+        pctl = _pctl_kind(kind)
+        out.append((kinds[kind] if pctl is None else pctl, _lib.SLOT_NAMES_X.index(slot)))
     return out
 
 
@@ -136,7 +160,7 @@ def sweep(args, out=sys.stdout) -> dict:
     import numpy as np
 
     from . import _lib
-    from .bote import DEFAULT_RANKING, DevicePlanet, MultiDeviceSearch, Sweep, max_key
+    from .bote import DEFAULT_RANKING, DevicePlanet, MultiDeviceSearch, Sweep, max_key, pctl_key
 
     planet = _planet(args)
     srv = np.arange(planet.R, dtype=np.uint32)
@@ -160,17 +184,19 @@ def sweep(args, out=sys.stdout) -> dict:
     def regions(rank):
         return [planet.names[i] for i in _lib.colex_unrank(int(rank), args.n, planet.R)]
 
-    names = {_lib.OBJ_SCORE: "score", _lib.OBJ_MEAN: "mean", _lib.OBJ_COV: "cov", _lib.OBJ_MAX: "max"}
-
     def record(kind, key, rank):
         rec = {"key": str(key), "rank": rank, "regions": regions(rank)}
         if kind == _lib.OBJ_MAX:  # the composite key's halves
             rec["max"], rec["sum"] = max_key(key)
+        elif _lib.is_pctl(kind):  # Histogram::percentile's f64 (a midpoint may end in .5)
+            twice, rec["sum"] = pctl_key(key)
+            rec["percentile"] = twice / 2
+            rec = {k: rec[k] for k in ("key", "rank", "regions", "percentile", "sum")}
         return rec
 
     doc = {"regions": planet.R, "n": args.n, "rank_begin": rb, "rank_end": re, "configs": re - rb,
            "keys": args.keys, "gpus": args.gpus, "valid": res.valid, "digest": str(res.digest),
-           "objectives": [{"objective": names[k] + ("" if k == _lib.OBJ_SCORE else ":" + _lib.SLOT_NAMES_X[s]),
+           "objectives": [{"objective": _objective_name(k) + ("" if k == _lib.OBJ_SCORE else ":" + _lib.SLOT_NAMES_X[s]),
                            "top": [record(k, key, rank) for key, rank in res.tops[o][:args.show]]}
                           for o, (k, s) in enumerate(objs)]}
     print(json.dumps(doc, indent=None if args.compact else 1), file=out)

@@ -155,6 +155,16 @@ uint32_t bote_max_f(uint32_t n) { return std::min(n / 2, 2u); }
 
 uint64_t bote_binomial(uint32_t ns, uint32_t n) { return binom_u64(ns, n); }
 
+int bote_percentile_index(uint32_t bp, uint32_t count, uint32_t* out_idx, int* out_whole) {
+  uint32_t idx;
+  bool whole;
+  if (!out_idx || !out_whole) return fail(BOTE_E_ARG, "null argument");
+  if (!percentile_index(bp, count, idx, whole)) return fail(BOTE_E_ARG, "percentile needs 1 <= bp <= 9999 and count >= 1");
+  *out_idx = idx;
+  *out_whole = whole ? 1 : 0;
+  return BOTE_OK;
+}
+
 int bote_colex_unrank(uint64_t rank, uint32_t n, uint32_t ns, uint32_t* out) {
   if (!out || n > ns) return fail(BOTE_E_ARG, "bad unrank arguments");
   if (!colex_unrank(rank, n, ns, out)) return fail(BOTE_E_ARG, "rank out of range");

@@ -45,6 +45,19 @@ int bote_sweep_create_ex(const bote_planet* p, const uint32_t* servers, uint32_t
 // behind them is bote_host.cpp's (fast_limits, score_bands, ...).  Step 1,
 // before anything is allocated, is its argument check (check_sweep_args).
 
+// A percentile objective as the kernels take it (bote_kernels.hpp OBJ_PCTL):
+// which of the slot's largest values, and whether its neighbour is added,
+// from bp and the slot's count (check_sweep_args admitted both).
+static uint32_t pctl_device_kind(uint32_t bp, uint32_t count) {
+  uint32_t idx = 0;
+  bool whole = false;
+  percentile_index(bp, count, idx, whole);
+  // idx == 0 is the least value itself (x = p * count > 0 is then no integer)
+  return bote::OBJ_PCTL | (whole && idx ? bote::PCTL_WHOLE : 0u) | percentile_need(bp, count);
+}
+static_assert(PCTL_MAX_NEED == (uint32_t)bote::PCTL_DEPTH && bote::PCTL_DEPTH <= (int)bote::PCTL_NEED_MASK,
+              "the admitted need fits the generic kernel's list and the encoding");
+
 // Step 2: the server, client and binomial lists on the device, the generic
 // kernel's arguments (s->args) and its launch geometry.
 static int sweep_upload_lists(bote_sweep* s, const uint32_t* servers, const uint32_t* clients,
@@ -73,7 +86,9 @@ static int sweep_upload_lists(bote_sweep* s, const uint32_t* servers, const uint
   fill_rank_params(a, has_score ? rp : nullptr);
   a.n_obj = (int)n_obj;
   for (uint32_t o = 0; o < n_obj; ++o) {
-    a.obj_kind[o] = objs[o].kind;
+    a.obj_kind[o] = is_percentile_kind(objs[o].kind)
+                        ? pctl_device_kind(objs[o].kind & 0xFFFF, slot_count(objs[o].slot, nc, n))
+                        : objs[o].kind;
     a.obj_slot[o] = objs[o].slot;
   }
   a.K = s->K;
@@ -86,7 +101,9 @@ static int sweep_upload_lists(bote_sweep* s, const uint32_t* servers, const uint
   s->shm = bote::eval_smem_bytes(a, n, s->bd, true);
   a.out_top = nullptr;
   if (s->shm > device_max_lds(p->device)) return fail(BOTE_E_RANGE, "planet/client set too large for LDS");
-  int nb = bote::eval_occupancy(n, false, s->bd, s->shm, keys != 0);
+  bool pctl = false;
+  for (uint32_t o = 0; o < n_obj; ++o) pctl = pctl || a.obj_kind[o] >= bote::OBJ_PCTL;
+  int nb = bote::eval_occupancy(n, false, s->bd, s->shm, keys != 0, pctl);
   s->grid = (uint32_t)(device_cus(p->device) * nb);
   s->xgrid = 32;
   return BOTE_OK;
@@ -280,10 +297,18 @@ static int sweep_plan_fast(bote_sweep* s, const uint32_t* servers, const uint32_
   // objective set, compiled into it, and moments that fit its 32-bit
   // arithmetic: FastLimits::keys32) or on the generic kernel
   const bool compiled_objs = is_compiled_objective_set(a.obj_kind, a.obj_slot, s->n_obj, keys);
-  // a MAX objective: the TAIL variant of the fast kernel (base key set), else
-  // the generic kernel
-  s->tail = false;
-  for (uint32_t o = 0; o < s->n_obj; ++o) s->tail = s->tail || a.obj_kind[o] == BOTE_OBJ_MAX;
+  // a MAX objective: the worst-client variant of the fast kernel (base key
+  // set), else the generic kernel; a percentile objective: its list variant
+  // when every one needs at most PCTL_FAST_DEPTH values, else the generic kernel
+  s->tail = bote::FAST_PLAIN;
+  uint32_t need = 0;
+  for (uint32_t o = 0; o < s->n_obj; ++o) {
+    if (a.obj_kind[o] == BOTE_OBJ_MAX) s->tail = std::max(s->tail, (int)bote::FAST_MAX);
+    if (a.obj_kind[o] >= bote::OBJ_PCTL) {
+      s->tail = bote::FAST_LIST;
+      need = std::max(need, a.obj_kind[o] & bote::PCTL_NEED_MASK);
+    }
+  }
   const FastLimits lim = fast_limits(p->lat.data(), p->R, nc, n);
   if (keys && eligible &&
       (!bote::group_supports_keys(n, bote::GROUP_XK_MAX_BD) || !compiled_objs || !lim.keys32 ||
@@ -291,6 +316,12 @@ static int sweep_plan_fast(bote_sweep* s, const uint32_t* servers, const uint32_
     if (kernel == BOTE_KERNEL_FAST || kernel == BOTE_KERNEL_GROUP)
       return fail(BOTE_E_ARG, "the extended key set runs on the group kernel (n = 4..7, config 5's "
                               "objectives) or the generic kernel");
+    s->path = Path::Generic;
+  }
+  if (need > (uint32_t)bote::PCTL_FAST_DEPTH && s->path != Path::Generic) {
+    if (kernel == BOTE_KERNEL_FAST)
+      return fail(BOTE_E_ARG, "the fast kernel's percentile lists are 4 deep: an objective needs " +
+                                  std::to_string(need) + " of its slot's largest values (generic kernel)");
     s->path = Path::Generic;
   }
   if (s->path == Path::Generic) return BOTE_OK;

@@ -293,6 +293,9 @@ __device__ __forceinline__ uint64_t cov_key(const Mom& m) {
 // MAX objective key (BOTE_OBJ_MAX): the slot's largest value, then its exact
 // sum (max <= 2 * 16383 and S1 < 2^27: include/bote_hip.h).
 __device__ __forceinline__ uint64_t max_key(uint32_t mx, uint64_t s1) { return ((uint64_t)mx << 32) | s1; }
+// Percentile objective key (BOTE_OBJ_PCTL): twice the percentile (an exact
+// integer <= 4 * 16383), then the slot's exact sum.
+__device__ __forceinline__ uint64_t pctl_key(uint32_t twice, uint64_t s1) { return ((uint64_t)twice << 32) | s1; }
 
 // Per-config digest, summed over configs mod 2^64.  A linear
 // fold of 32-bit words, each times its own constant as two 16-bit halves (one

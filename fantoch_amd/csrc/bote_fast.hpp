@@ -27,10 +27,11 @@ __device__ __forceinline__ void defer_rank(const FastArgs& a, uint64_t rank) {
 // block's current K-th record per objective (only .key is read).  Returns
 // false when a COV decision is within the ambiguity band: the caller defers
 // the config and offers nothing to the top-K.  TAIL (the fast kernel's
-// worst-client variant): a MAX objective's key and ok are left as the caller,
-// which holds the slots' maxima, set them; without it no objective has that
-// kind.
-template <int N, bool TAIL = false>
+// variant, FAST_*): with FAST_MAX a MAX objective's key and ok are left as
+// the caller, which holds the slots' maxima, set them; with FAST_LIST a MAX or
+// percentile objective's, from the caller's sorted lists; with FAST_PLAIN no
+// objective has those kinds.
+template <int N, int TAIL = FAST_PLAIN>
 __device__ __forceinline__ bool finish_config(const FastArgs& a, const Mom (&mom)[NSLOT], double vcol_lead,
                                               uint32_t lead_member, uint64_t rank, const Rec* thr, double pnc1,
                                               double pnc2, uint64_t& valid_cnt, uint64_t& digest,
@@ -126,7 +127,8 @@ __device__ __forceinline__ bool finish_config(const FastArgs& a, const Mom (&mom
       }
       continue;
     }
-    if (TAIL && kind == OBJ_MAX) continue;
+    if (TAIL == FAST_MAX && kind == OBJ_MAX) continue;
+    if (TAIL == FAST_LIST && kind >= OBJ_MAX) continue;
 #pragma unroll
     for (int q = 0; q < NSLOT; ++q) {
       if ((uint32_t)q != sl) continue;

@@ -396,6 +396,32 @@ bool slot_exists_n(uint32_t n, uint32_t slot, uint32_t keys) {
   return slot == 18 || f2;
 }
 
+uint32_t slot_count(uint32_t slot, uint32_t nc, uint32_t n) {
+  const bool colocated = (slot >= 5 && slot < 10) || (slot >= 14 && slot < 18);
+  return colocated ? n : nc;
+}
+
+bool is_percentile_kind(uint32_t kind) { return (kind >> 16) == 1 && (kind & 0xFFFF) >= 1 && (kind & 0xFFFF) <= 9999; }
+
+bool percentile_index(uint32_t bp, uint32_t count, uint32_t& idx, bool& whole) {
+  if (bp < 1 || bp > 9999 || count == 0) return false;
+  // (volatile: each step is one rounded f64 operation whatever the flags)
+  volatile double p = (double)bp / 10000.0;
+  volatile double x = p * (double)count;
+  volatile double r = std::round(x);
+  volatile double d = x - r;
+  idx = (uint32_t)r;
+  whole = d == 0.0;
+  return true;
+}
+
+uint32_t percentile_need(uint32_t bp, uint32_t count) {
+  uint32_t idx;
+  bool whole;
+  if (!percentile_index(bp, count, idx, whole)) return 0;
+  return count - std::max(idx, 1u) + 1;
+}
+
 bool chunk_states(const uint64_t* starts, uint32_t count, uint32_t n, uint32_t ns, std::vector<uint64_t>& out) {
   const uint32_t F = n - 3;
   out.assign((size_t)count * 4, 0);
@@ -607,9 +633,11 @@ Status check_sweep_args(uint32_t R, const uint32_t* servers, uint32_t ns, const 
   if (n_obj > BOTE_MAX_OBJECTIVES) return fail(BOTE_E_RANGE, "more than 8 objectives");
   if (n_obj && !objs) return fail(BOTE_E_ARG, "objectives null");
   if (K == 0 || K > BOTE_MAX_K) return fail(BOTE_E_RANGE, "K must be in [1, 128]");
-  bool has_max = false;
+  bool has_max = false, has_pctl = false;
   for (uint32_t o = 0; o < n_obj; ++o) {
-    if (objs[o].kind > BOTE_OBJ_COV && objs[o].kind != BOTE_OBJ_MAX) return fail(BOTE_E_ARG, "unknown objective kind");
+    const bool pctl = is_percentile_kind(objs[o].kind);
+    if (objs[o].kind > BOTE_OBJ_COV && objs[o].kind != BOTE_OBJ_MAX && !pctl)
+      return fail(BOTE_E_ARG, "unknown objective kind");
     if (objs[o].kind == BOTE_OBJ_SCORE) {
       has_score = true;
       continue;
@@ -617,10 +645,17 @@ Status check_sweep_args(uint32_t R, const uint32_t* servers, uint32_t ns, const 
     if (objs[o].slot >= (keys ? BOTE_NSLOTS_X : BOTE_NSLOTS)) return fail(BOTE_E_ARG, "slot out of range");
     if (!slot_exists_n(n, objs[o].slot, keys)) return fail(BOTE_E_ARG, "slot does not exist for this n (max_f < 2)");
     has_max = has_max || objs[o].kind == BOTE_OBJ_MAX;
+    if (pctl) {
+      has_pctl = true;
+      if (percentile_need(objs[o].kind & 0xFFFF, slot_count(objs[o].slot, nc, n)) > PCTL_MAX_NEED)
+        return fail(BOTE_E_RANGE, "percentile needs more than 8 of the slot's largest values");
+    }
   }
   // (after the objectives: a bad kind or slot is reported whatever the path)
   if (has_max && kernel == BOTE_KERNEL_GROUP)
     return fail(BOTE_E_ARG, "the group kernel does not compute MAX objectives (fast or generic kernel)");
+  if (has_pctl && kernel == BOTE_KERNEL_GROUP)
+    return fail(BOTE_E_ARG, "the group kernel does not compute percentile objectives (fast or generic kernel)");
   if (has_score && !rp) return fail(BOTE_E_ARG, "SCORE objective needs ranking params");
   if (rp) return check_ft_metric(rp->ft_metric);
   return OK;

@@ -138,6 +138,23 @@ bool is_compiled_objective_set(const uint32_t* kinds, const uint32_t* slots, uin
 // Slot `slot` exists for config size n (f = 2 keys need max_f >= 2); slots
 // >= 10 only with the extended key set.
 bool slot_exists_n(uint32_t n, uint32_t slot, uint32_t keys);
+// The values a slot's histogram holds: the n members for the colocated slots
+// (5..9, 14..17), the nc Input clients for every other slot.
+uint32_t slot_count(uint32_t slot, uint32_t nc, uint32_t n);
+
+// ----------------------------------------------- percentile objectives --
+// BOTE_OBJ_PCTL(bp): (kind >> 16) == 1 with the low half in 1..9999.
+constexpr uint32_t PCTL_MAX_NEED = 8;  // the generic kernel's list depth
+bool is_percentile_kind(uint32_t kind);
+// Histogram::percentile's index (histogram.rs:110-170) for p = bp / 10000.0
+// over `count` values: x = p * count in one f64 multiply (this file is built
+// without contraction), idx = round(x) half away from zero, whole = (x - idx
+// == 0.0).  False unless 1 <= bp <= 9999 and count >= 1.
+bool percentile_index(uint32_t bp, uint32_t count, uint32_t& idx, bool& whole);
+// How many of the largest values decide it: count - max(idx, 1) + 1.  The
+// percentile is the need-th largest; when `whole` (idx >= 1 then), the mean of
+// that one and the (need - 1)-th largest.  0 for bad arguments.
+uint32_t percentile_need(uint32_t bp, uint32_t count);
 
 // Per start rank, the 4 u64 of FastArgs::wstate: the colex rank of the
 // config's n - 3 largest positions (its group: the config with its three
@@ -208,8 +225,10 @@ Status check_leaderless_args(uint32_t R, const uint32_t* servers, uint32_t ns, c
 // bote_sweep_create_keys; has_score: some objective is BOTE_OBJ_SCORE.  In
 // order: the key set, the kernel path, check_search_args, the objective
 // count, a null list, K, then per objective its kind, slot range and slot
-// existence for n; then a MAX objective on a forced group kernel (which does
-// not compute it), SCORE without ranking params, and the ft_metric.
+// existence for n and, for a percentile, that it needs at most PCTL_MAX_NEED
+// of the slot's largest values; then a MAX objective on a forced group kernel
+// (which does not compute it), a percentile objective on one, SCORE without
+// ranking params, and the ft_metric.
 Status check_sweep_args(uint32_t R, const uint32_t* servers, uint32_t ns, const uint32_t* clients, uint32_t nc,
                         uint32_t n, const bote_objective* objs, uint32_t n_obj, uint32_t K,
                         const bote_ranking_params* rp, int kernel, uint32_t keys, bool& has_score);

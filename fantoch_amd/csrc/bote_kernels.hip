@@ -93,12 +93,15 @@ __device__ __forceinline__ uint32_t sel(const uint32_t (&arr)[N], uint32_t i) {
 
 // --------------------------------------------------------- config result --
 // X: the extended key set (slots 10..19 and every leader's FPaxos moments,
-// al[f - 1][config-order leader], Input clients)
-template <int N, bool X>
+// al[f - 1][config-order leader], Input clients); PCTL: a top-K sweep with a
+// percentile objective (its own instantiations: the others keep their code
+// and registers)
+template <int N, bool X, bool PCTL = false>
 struct CfgOut {
   static constexpr int NS = X ? NSLOT_X : NSLOT;
   Mom mom[NS];
   uint32_t mx[NS];  // Histogram::max per slot (top-K sweeps only: the MAX keys)
+  uint32_t pt[PCTL ? MAXOBJ : 1];  // PCTL: twice Histogram::percentile per percentile objective
   Mom al[X ? 2 : 1][X ? N : 1];
   uint32_t lead_orig;
   double score;
@@ -114,9 +117,9 @@ __device__ __forceinline__ bool slot_has(int s) {
 // ------------------------------------------------------------- eval one ---
 // Evaluate the configuration whose members are positions p[0..N) of the
 // server list (given order = config order).  `oi` is the output row (FULL).
-template <int N, bool FULL, bool X>
+template <int N, bool FULL, bool X, bool PCTL = false>
 __device__ __forceinline__ void eval_config(const EvalArgs& a, const Smem& s, const uint32_t (&p)[N], bool sorted_in, uint64_t oi,
-                            CfgOut<N, X>& out) {
+                            CfgOut<N, X, PCTL>& out) {
   using QC = QCfg<N>;
   using QT = QTab<N, X>;
   constexpr int NL = QT::NT;  // leaderless tables: compute_stats' q's, then the extended ones
@@ -362,11 +365,13 @@ __device__ __forceinline__ void eval_config(const EvalArgs& a, const Smem& s, co
       }
     }
   }
+  uint32_t flreg[2] = {0, 0}, flq[2] = {0, 0};  // X: the best leaders by mean (region, quorum latency)
   if constexpr (X) {
     // FPaxos all leaders (Bote::all_leaders_stats, lib.rs:129-150), Input
     // clients, q = f + 1, leaders in config order, and the best leader by
     // Stats::Mean (lib.rs:99-121: the first minimum, exact sums)
     uint32_t alm[2][N] = {};  // the leaders' worst clients
+    uint32_t alr[N], alq[2][N];  // their regions and quorum latencies
 #pragma unroll
     for (int o = 0; o < N; ++o) {
       uint32_t l = 0;
@@ -377,6 +382,11 @@ __device__ __forceinline__ void eval_config(const EvalArgs& a, const Smem& s, co
       const uint64_t q1 = sel(Qf1, l), q2 = sel(Qf2, l);
       out.al[0][o] = leader_mom(c1, c2, nc, q1);
       out.al[1][o] = leader_mom(c1, c2, nc, q2);
+      if constexpr (PCTL) {
+        alr[o] = sel(mreg, l);
+        alq[0][o] = (uint32_t)q1;
+        alq[1][o] = (uint32_t)q2;
+      }
       if (!FULL) {
         const uint32_t cm = s.cmx[pl];
         alm[0][o] = cm + (uint32_t)q1;
@@ -385,15 +395,28 @@ __device__ __forceinline__ void eval_config(const EvalArgs& a, const Smem& s, co
     }
     Mom b1 = out.al[0][0], b2 = out.al[1][0];
     uint32_t m1 = alm[0][0], m2 = alm[1][0];
+    if constexpr (PCTL) {
+      flreg[0] = flreg[1] = alr[0];
+      flq[0] = alq[0][0];
+      flq[1] = alq[1][0];
+    }
 #pragma unroll
     for (int o = 1; o < N; ++o) {
       if (out.al[0][o].s1 < b1.s1) {
         b1 = out.al[0][o];
         m1 = alm[0][o];
+        if constexpr (PCTL) {
+          flreg[0] = alr[o];
+          flq[0] = alq[0][o];
+        }
       }
       if (out.al[1][o].s1 < b2.s1) {
         b2 = out.al[1][o];
         m2 = alm[1][o];
+        if constexpr (PCTL) {
+          flreg[1] = alr[o];
+          flq[1] = alq[1][o];
+        }
       }
     }
     out.mom[SLOT_FL1] = b1;
@@ -401,6 +424,86 @@ __device__ __forceinline__ void eval_config(const EvalArgs& a, const Smem& s, co
     if (!FULL) {
       out.mx[SLOT_FL1] = m1;
       out.mx[SLOT_FL2] = m2;
+    }
+  }
+
+  // --- Percentile objectives (Histogram::percentile, histogram.rs:110-170):
+  //     one more pass over the objective's slot (uniform across lanes) per
+  //     objective, keeping the slot's PCTL_DEPTH largest values in a sorted
+  //     register list that the next objective reuses.  The values are
+  //     regenerated as the passes above made them: leaderless from the nearest
+  //     member and the lane's quorum table, FPaxos from the leader's column.
+  if constexpr (PCTL) {
+#pragma unroll 1
+    for (int o = 0; o < a.n_obj; ++o) {
+      const uint32_t kind = a.obj_kind[o], sl = a.obj_slot[o];
+      if (kind < OBJ_PCTL) continue;
+      const uint32_t need = kind & PCTL_NEED_MASK;
+      uint32_t L[PCTL_DEPTH];  // descending
+#pragma unroll
+      for (int i = 0; i < PCTL_DEPTH; ++i) L[i] = 0;
+      auto put = [&](uint32_t v) {
+#pragma unroll
+        for (int i = 0; i < PCTL_DEPTH; ++i) {
+          const uint32_t hi = max(L[i], v);
+          v = min(L[i], v);
+          L[i] = hi;
+        }
+      };
+      const bool colocated = (sl >= 5 && sl < 10) || (sl >= 14 && sl < 18);
+      // the slot's protocol: 0 af1, 1 ff1, 2 af2, 3 ff2, 4 e, then the
+      // extended set's 5 tt1, 6 tt2, 7 tw1, 8 tw2, 9 fl1, 10 fl2
+      const uint32_t b = sl < 10 ? sl % 5 : sl < 18 ? 5 + (sl - 10) % 4 : 9 + (sl - 18);
+      int ti = -1;  // leaderless: the quorum table
+      uint32_t lr = lreg, lq = lq1;  // FPaxos: the leader's region and quorum latency
+      if (b == 0) ti = QC::idx_a1;
+      else if (b == 2) ti = QC::idx_a2;
+      else if (b == 4) ti = QC::idx_e;
+      else if (b == 3) lq = lq2;
+      if constexpr (X) {
+        if (b == 5 || b == 7) ti = QT::idx(2);
+        else if (b == 6) ti = QT::idx(4) < 0 ? 0 : QT::idx(4);
+        else if (b == 8) ti = QT::idx(3) < 0 ? 0 : QT::idx(3);
+        else if (b >= 9) {
+          lr = b == 9 ? flreg[0] : flreg[1];
+          lq = b == 9 ? flq[0] : flq[1];
+        }
+      }
+      if (ti >= 0) {
+        const uint32_t w = (uint32_t)ti >> 1, sh = ((uint32_t)ti & 1) * 16;
+        auto value = [&](uint32_t m) {  // m: nearest member's (latency << 4 | member)
+          return (m >> LAT_SHIFT) + ((s.qtab[((m & 15) * NLW + w) * BD + tid] >> sh) & 0xFFFFu);
+        };
+        if (colocated) {
+#pragma unroll
+          for (int k = 0; k < N; ++k) put(value(cdk[k]));
+        } else {
+          for (uint32_t c = 0; c < nc; ++c) {
+            const uint32_t off = s.clioff[c];
+            uint32_t m = 0xFFFFFFFFu;
+#pragma unroll
+            for (int k = 0; k < N; ++k) m = min(m, s.mat[off + mreg[k]] | (uint32_t)k);
+            put(value(m));
+          }
+        }
+      } else if (colocated) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) put((s.mat[moff[k] + lr] >> LAT_SHIFT) + lq);
+      } else {
+        for (uint32_t c = 0; c < nc; ++c) put((s.mat[s.clioff[c] + lr] >> LAT_SHIFT) + lq);
+      }
+      // the need-th largest, and the one above it (need <= the slot's count,
+      // so neither is a list entry no value reached)
+      uint32_t v = 0, up = 0;
+#pragma unroll
+      for (int i = 0; i < PCTL_DEPTH; ++i) {
+        if ((uint32_t)i + 1 == need) v = L[i];
+        if ((uint32_t)i + 2 == need) up = L[i];
+      }
+      const uint32_t twice = (kind & PCTL_WHOLE) ? v + up : 2 * v;
+#pragma unroll
+      for (int q = 0; q < MAXOBJ; ++q)
+        if (q == o) out.pt[q] = twice;
     }
   }
 
@@ -466,8 +569,9 @@ __device__ __forceinline__ void eval_config(const EvalArgs& a, const Smem& s, co
 }
 
 // ------------------------------------------------------------ the kernel --
-template <int N, bool FULL, bool X>
+template <int N, bool FULL, bool X, bool PCTL = false>
 __global__ void __launch_bounds__(256) eval_kernel(EvalArgs a) {
+  static_assert(!(FULL && PCTL), "percentile objectives belong to top-K sweeps");
   constexpr int NLW = (QTab<N, X>::NT + 1) / 2;
   constexpr int NS = CfgOut<N, X>::NS;
   extern __shared__ __align__(16) unsigned char smem[];
@@ -543,9 +647,9 @@ __global__ void __launch_bounds__(256) eval_kernel(EvalArgs a) {
     }
     for (uint64_t t = 0; t < runlen; ++t) {
       const bool have = jobok && rank < rend;
-      CfgOut<N, X> r;
+      CfgOut<N, X, PCTL> r;
       if (have) {
-        eval_config<N, FULL, X>(a, s, p, sorted_in, rank - a.rb, r);
+        eval_config<N, FULL, X, PCTL>(a, s, p, sorted_in, rank - a.rb, r);
         if (r.valid) ++valid_cnt;
         if (a.want_digest) {
           uint32_t h = 0;
@@ -608,10 +712,14 @@ __global__ void __launch_bounds__(256) eval_kernel(EvalArgs a) {
               // registers (a select chain here gets turned into scratch).
 #pragma unroll
               for (int q = 0; q < NS; ++q)
-                if ((uint32_t)q == sl)
-                  key[o] = kind == OBJ_MEAN  ? r.mom[q].s1
-                           : kind == OBJ_MAX ? max_key(r.mx[q], r.mom[q].s1)
-                                             : cov_key(r.mom[q]);
+                if ((uint32_t)q == sl) {
+                  if (PCTL && kind >= OBJ_PCTL)
+                    key[o] = pctl_key(r.pt[o], r.mom[q].s1);
+                  else
+                    key[o] = kind == OBJ_MEAN  ? r.mom[q].s1
+                             : kind == OBJ_MAX ? max_key(r.mx[q], r.mom[q].s1)
+                                               : cov_key(r.mom[q]);
+                }
             }
           }
         }
@@ -742,10 +850,13 @@ size_t eval_smem_bytes(const EvalArgs& a, uint32_t n, uint32_t bd, bool topk) {
 
 // the kernel for config size n, full outputs or top-K, base or extended keys
 // (null: unsupported n), for the occupancy query and the launch alike
-static const void* eval_fn(uint32_t n, bool full, bool keys) {
+// `pctl`: the top-K instantiation that also computes percentile objectives
+static const void* eval_fn(uint32_t n, bool full, bool keys, bool pctl) {
   switch (n) {
 #define FN_CASE(NN)                                                                                             \
   case NN:                                                                                                      \
+    if (pctl && !full)                                                                                          \
+      return keys ? (const void*)eval_kernel<NN, false, true, true> : (const void*)eval_kernel<NN, false, false, true>; \
     return keys ? (full ? (const void*)eval_kernel<NN, true, true> : (const void*)eval_kernel<NN, false, true>) \
                 : (full ? (const void*)eval_kernel<NN, true, false> : (const void*)eval_kernel<NN, false, false>);
     FN_CASE(2) FN_CASE(3) FN_CASE(4) FN_CASE(5) FN_CASE(6) FN_CASE(7) FN_CASE(8) FN_CASE(9)
@@ -755,14 +866,16 @@ static const void* eval_fn(uint32_t n, bool full, bool keys) {
   }
 }
 
-int eval_occupancy(uint32_t n, bool full, uint32_t bd, size_t shm, bool keys) {
-  const void* k = eval_fn(n, full, keys);
+int eval_occupancy(uint32_t n, bool full, uint32_t bd, size_t shm, bool keys, bool pctl) {
+  const void* k = eval_fn(n, full, keys, pctl);
   return k ? kernel_occupancy(k, bd, shm, 1) : 0;
 }
 
 hipError_t launch_eval(const EvalArgs& a, uint32_t n, bool full, uint32_t grid, uint32_t bd, size_t shm,
                        hipStream_t st) {
-  const void* k = eval_fn(n, full, a.keys != 0);
+  bool pctl = false;  // a percentile objective among a top-K sweep's (bote_kernels.hpp OBJ_PCTL)
+  for (int o = 0; o < a.n_obj && !full; ++o) pctl = pctl || a.obj_kind[o] >= OBJ_PCTL;
+  const void* k = eval_fn(n, full, a.keys != 0, pctl);
   return k ? launch_kernel(k, a, grid, bd, shm, st) : hipErrorInvalidValue;
 }
 

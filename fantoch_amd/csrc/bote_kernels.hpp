@@ -9,6 +9,15 @@ constexpr int NSLOT = 10;
 constexpr int G_MERGE_LISTS = 8;  // lists merged per workgroup
 enum { SLOT_AF1 = 0, SLOT_FF1 = 1, SLOT_AF2 = 2, SLOT_FF2 = 3, SLOT_E = 4 };
 enum { OBJ_SCORE = 0, OBJ_MEAN = 1, OBJ_COV = 2, OBJ_MAX = 16 };
+// A percentile objective (BOTE_OBJ_PCTL) as the kernels see it in obj_kind:
+// the host (bote_capi_sweep.hip, pctl_device_kind) turns bp and the slot's
+// count into OBJ_PCTL | (whole ? PCTL_WHOLE : 0) | need, need = 1..PCTL_DEPTH:
+// twice the percentile is 2 * (the need-th largest value of the slot), or with
+// `whole` that value plus the (need - 1)-th largest.  Every other kind is
+// below OBJ_PCTL.
+constexpr uint32_t OBJ_PCTL = 0x10000u, PCTL_WHOLE = 16u, PCTL_NEED_MASK = 15u;
+constexpr int PCTL_DEPTH = 8;       // the generic kernel's sorted list
+constexpr int PCTL_FAST_DEPTH = 4;  // the fast kernel's list variant
 
 struct EvalArgs {
   // planet (device): latency << 4, row = from
@@ -208,13 +217,16 @@ struct FastArgs {
 #else
 #define ABLATE(a, bit) false
 #endif
-// `tail`: the TAIL variant of the fast kernel, which also carries every
-// slot's maximum (the worst client) for BOTE_OBJ_MAX objectives; the plain
-// kernel treats no such objective
-size_t fast_smem_bytes(const FastArgs& a, uint32_t n, bool tail);
-int fast_occupancy(uint32_t n, bool tail, size_t shm);
+// `tail`: the variant of the fast kernel.  FAST_PLAIN treats no MAX or
+// percentile objective; FAST_MAX also carries every slot's maximum (the worst
+// client) for BOTE_OBJ_MAX objectives; FAST_LIST carries every slot's
+// PCTL_FAST_DEPTH largest values, descending, for percentile objectives of
+// need <= PCTL_FAST_DEPTH (entry 0 serves the MAX objectives of such a sweep)
+enum { FAST_PLAIN = 0, FAST_MAX = 1, FAST_LIST = 2 };
+size_t fast_smem_bytes(const FastArgs& a, uint32_t n, int tail);
+int fast_occupancy(uint32_t n, int tail, size_t shm);
 // (e0, e1: events carried by the dispatch itself, bote_launch.hpp, for a timed launch)
-hipError_t launch_fast(const FastArgs& a, uint32_t n, bool tail, uint32_t grid, size_t shm, hipStream_t st,
+hipError_t launch_fast(const FastArgs& a, uint32_t n, int tail, uint32_t grid, size_t shm, hipStream_t st,
                        hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
 size_t group_smem_bytes(const FastArgs& a, uint32_t n);
 bool group_uses_lines(uint32_t n);  // n <= 7: client lines (FastArgs::gslots) and register lookups
@@ -237,7 +249,8 @@ hipError_t launch_group(const FastArgs& a, uint32_t n, bool def_objectives, uint
 
 // ---- generic exact kernel (bote_kernels.hip)
 size_t eval_smem_bytes(const EvalArgs& a, uint32_t n, uint32_t bd, bool topk);
-int eval_occupancy(uint32_t n, bool full, uint32_t bd, size_t shm, bool keys = false);
+// (pctl: the top-K instantiation launch_eval takes for a sweep with a percentile objective)
+int eval_occupancy(uint32_t n, bool full, uint32_t bd, size_t shm, bool keys = false, bool pctl = false);
 hipError_t launch_eval(const EvalArgs& a, uint32_t n, bool full, uint32_t grid, uint32_t bd, size_t shm,
                        hipStream_t st);
 

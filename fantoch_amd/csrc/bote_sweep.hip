@@ -41,11 +41,12 @@ struct FastSmem {
   uint64_t* cs2;
   double* vcol;
   uint64_t* binom;
-  uint32_t* cmax;  // TAIL: per position, the largest client latency of its column
+  uint32_t* cmax;  // FAST_MAX: per position, the largest client latency of its column
+  uint2* c4;       // FAST_LIST: per position, its column's four largest client latencies, descending (4 x u16)
   TopkLds tk;
 };
 
-__host__ __device__ inline size_t fast_layout(const FastArgs& a, int N, int NLW, bool tail, size_t* off) {
+__host__ __device__ inline size_t fast_layout(const FastArgs& a, int N, int NLW, int tail, size_t* off) {
   size_t o = 0;
   off[0] = o; o += (size_t)N * FAST_BD * NLW * 4;  // qtab first: offsets stay small
   off[1] = o; o += (size_t)a.R * a.cq_stride * 8;
@@ -62,12 +63,13 @@ __host__ __device__ inline size_t fast_layout(const FastArgs& a, int N, int NLW,
   off[10] = o; o += (size_t)KP * 16;          // tmp
   off[11] = o; o += (size_t)MAXOBJ * 16;      // thr
   off[12] = o; o += 48;                       // cnt[1 + MAXOBJ]
-  off[13] = o; o += tail ? (size_t)a.ns * 4 : 0;  // cmax
+  off[13] = o; o += tail == FAST_MAX ? (size_t)a.ns * 4 : 0;   // cmax
+  off[14] = o; o += tail == FAST_LIST ? (size_t)a.ns * 8 : 0;  // c4 (8-byte aligned: every region above is)
   return o;
 }
 
-size_t fast_smem_bytes(const FastArgs& a, uint32_t n, bool tail) {
-  size_t off[14];
+size_t fast_smem_bytes(const FastArgs& a, uint32_t n, int tail) {
+  size_t off[15];
   int nl = 0;
   switch (n) {
 #define NL_CASE(NN) case NN: nl = QCfg<NN>::NL; break;
@@ -88,6 +90,38 @@ __device__ __forceinline__ uint32_t sel_u(const uint32_t (&arr)[N], uint32_t i) 
 }
 
 
+// ------------------------------------------------- sorted lists (LIST) ----
+// A slot's four largest values, descending, as 4 x u16 in two words (the fast
+// path's values are at most 2 * 4095): l[0] = v0 | v1 << 16, l[1] = v2 | v3 << 16.
+static_assert(PCTL_FAST_DEPTH == 4, "the packed lists and their merge are four deep");
+__device__ __forceinline__ void sort_desc(uint32_t& hi, uint32_t& lo) {
+  const uint32_t h = max(hi, lo);
+  lo = min(hi, lo);
+  hi = h;
+}
+// insert v into the descending list l (each 16-bit half its own list); the least drops out
+__device__ __forceinline__ void pk_insert(us2 (&l)[PCTL_FAST_DEPTH], us2 v) {
+#pragma unroll
+  for (int i = 0; i < PCTL_FAST_DEPTH; ++i) {
+    const us2 hi = __builtin_elementwise_max(l[i], v);
+    if (i + 1 < PCTL_FAST_DEPTH) v = __builtin_elementwise_min(l[i], v);
+    l[i] = hi;
+  }
+}
+__device__ __forceinline__ void list_insert(uint32_t (&l)[PCTL_FAST_DEPTH], uint32_t v) {
+#pragma unroll
+  for (int i = 0; i < PCTL_FAST_DEPTH; ++i) {
+    const uint32_t hi = max(l[i], v);
+    if (i + 1 < PCTL_FAST_DEPTH) v = min(l[i], v);
+    l[i] = hi;
+  }
+}
+// the k-th largest (k = 1..4, uniform) of a packed list
+__device__ __forceinline__ uint32_t list_at(const uint32_t (&l)[2], uint32_t k) {
+  const uint32_t w = k > 2 ? l[1] : l[0];
+  return (k & 1) ? (w & 0xFFFFu) : (w >> 16);
+}
+
 // ------------------------------------------------------------ hot loop ----
 // Input leaderless keys over client quads.  Per quad and member: one
 // ds_read_b64 (4 clients), a packed OR of the member index and a packed min
@@ -95,23 +129,37 @@ __device__ __forceinline__ uint32_t sel_u(const uint32_t (&arr)[N], uint32_t i) 
 // one qtab read for the nearest member's quorum latencies; packed adds and
 // v_dot2_u32_u16 accumulate the sum and the sum of squares.  Squares are
 // accumulated in 32 bits and flushed to 64 bits every `flushQ` quads.
-// TAIL: also each table's largest client latency into MX, one packed max
+// TAIL == FAST_MAX: also each table's largest client latency into MX, one packed max
 // (v_pk_max_u16) per half quad into a running register per table, taken after
 // the remainder mask (a dead client counts 0); no LDS traffic is added.
-template <int N, int NL, bool TAIL>
+// TAIL == FAST_LIST: each table's four largest client latencies into ML,
+// descending, as 4 x u16 in two words.  The loop keeps, per table, a descending
+// list of four packed registers: the low halves are one stream (clients 0 and
+// 2 of every quad), the high halves another (clients 1 and 3), and a masked
+// half quad is inserted into both at once by 7 packed compare-exchange steps
+// (v_pk_max_u16 / v_pk_min_u16).  After the loop the two streams' lists are
+// merged.  A dead client enters as 0 and cannot displace a live value among
+// the largest `need <= nc`.  No LDS traffic is added here either.
+template <int N, int NL, int TAIL>
 __device__ __forceinline__ void client_quads(const unsigned char* B, uint32_t cqt, uint32_t nq, uint32_t rem,
                                              uint32_t flushQ, const uint32_t (&colT)[N], uint32_t qlane,
-                                             uint32_t (&S1)[NL], uint64_t (&S2)[NL], uint32_t (&MX)[NL]) {
+                                             uint32_t (&S1)[NL], uint64_t (&S2)[NL], uint32_t (&MX)[NL],
+                                             uint32_t (&ML)[NL][2]) {
   const us2 ones = {1, 1};
   constexpr int NQ = NL == 3 ? 8 : 4;  // qtab words per quad
   uint32_t s2[NL];
-  us2 pm[NL];  // TAIL: running packed maxima
+  us2 pm[NL];  // FAST_MAX: running packed maxima
+  us2 pl[NL][PCTL_FAST_DEPTH];  // FAST_LIST: running packed lists, descending
 #pragma unroll
   for (int t = 0; t < NL; ++t) {
     S1[t] = 0;
     S2[t] = 0;
     s2[t] = 0;
-    if constexpr (TAIL) pm[t] = us2{0, 0};
+    if constexpr (TAIL == FAST_MAX) pm[t] = us2{0, 0};
+    if constexpr (TAIL == FAST_LIST) {
+#pragma unroll
+      for (int i = 0; i < PCTL_FAST_DEPTH; ++i) pl[t][i] = us2{0, 0};
+    }
   }
   uint32_t col[N];
 #pragma unroll
@@ -159,7 +207,11 @@ __device__ __forceinline__ void client_quads(const unsigned char* B, uint32_t cq
     S1[t] = __builtin_amdgcn_udot2(a23, ones, S1[t], false);
     s2[t] = __builtin_amdgcn_udot2(a01, a01, s2[t], false);
     s2[t] = __builtin_amdgcn_udot2(a23, a23, s2[t], false);
-    if constexpr (TAIL) pm[t] = __builtin_elementwise_max(__builtin_elementwise_max(pm[t], a01), a23);
+    if constexpr (TAIL == FAST_MAX) pm[t] = __builtin_elementwise_max(__builtin_elementwise_max(pm[t], a01), a23);
+    if constexpr (TAIL == FAST_LIST) {
+      pk_insert(pl[t], a01);
+      pk_insert(pl[t], a23);
+    }
   };
   auto accum = [&](us2 lo, us2 hi, const uint32_t (&q)[NQ], uint32_t mlo, uint32_t mhi) {
     const us2 dlo = lo >> (us2)4, dhi = hi >> (us2)4;
@@ -235,14 +287,30 @@ __device__ __forceinline__ void client_quads(const unsigned char* B, uint32_t cq
     quad(nq * 8, mlo, mhi);
     flush();
   }
-  if constexpr (TAIL) {
+  if constexpr (TAIL == FAST_MAX) {
 #pragma unroll
     for (int t = 0; t < NL; ++t) MX[t] = max((uint32_t)pm[t].x, (uint32_t)pm[t].y);
+  }
+  if constexpr (TAIL == FAST_LIST) {
+#pragma unroll
+    for (int t = 0; t < NL; ++t) {
+      // the four largest of two descending lists A and B: max(A[i], B[3 - i])
+      // holds them as a bitonic sequence, which two exchange stages sort
+      uint32_t c[PCTL_FAST_DEPTH];
+#pragma unroll
+      for (int i = 0; i < PCTL_FAST_DEPTH; ++i) c[i] = max((uint32_t)pl[t][i].x, (uint32_t)pl[t][PCTL_FAST_DEPTH - 1 - i].y);
+      sort_desc(c[0], c[2]);
+      sort_desc(c[1], c[3]);
+      sort_desc(c[0], c[1]);
+      sort_desc(c[2], c[3]);
+      ML[t][0] = c[0] | (c[1] << 16);
+      ML[t][1] = c[2] | (c[3] << 16);
+    }
   }
 }
 
 // ---------------------------------------------------------- the kernel ----
-// TAIL: the variant for sweeps with a MAX objective (base key set).  It also
+// TAIL == FAST_MAX: the variant for sweeps with a MAX objective (base key set).  It also
 // carries each slot's maximum: the Input leaderless tables' from the client
 // loop, Input FPaxos in closed form (the leader column's largest latency,
 // staged per position beside cs1/cs2, plus the quorum latency), and the
@@ -251,14 +319,24 @@ __device__ __forceinline__ void client_quads(const unsigned char* B, uint32_t cq
 // alone, and withdrawn when it defers the config: built after it, the ten
 // maxima stay live across the score and digest arithmetic and N = 7 spills
 // (8 B/lane of scratch; none this way).
-template <int N, bool TAIL>
+// TAIL == FAST_LIST: the variant for sweeps with a percentile objective that
+// needs at most four of its slot's largest values (base key set).  It carries
+// each slot's four largest values, descending, where FAST_MAX carries the
+// largest: the Input leaderless tables' from the client loop's packed lists,
+// Input FPaxos from the leader column's four largest latencies (staged per
+// position, c4) plus the quorum latency, the colocated leaderless from the
+// lane's quorum table read back after the client loop (nothing more is live
+// across it), colocated FPaxos from the N-step loop.  Entry 0 is the maximum,
+// so the MAX objectives of such a sweep are served from the lists.  Keys are
+// built and withdrawn as for FAST_MAX.
+template <int N, int TAIL>
 __global__ void __launch_bounds__(FAST_BD, 4) sweep_fast_kernel(FastArgs a) {
   using QC = QCfg<N>;
   constexpr int NL = QC::NL;
   constexpr int NLW = NL <= 2 ? 1 : 2;
   constexpr int P = Pow2<N - 1>::v;  // off-diagonal row values, padded
   extern __shared__ __align__(16) unsigned char smem[];
-  size_t off[14];
+  size_t off[15];
   fast_layout(a, N, NLW, TAIL, off);
   FastSmem s;
   s.base = smem;
@@ -271,6 +349,7 @@ __global__ void __launch_bounds__(FAST_BD, 4) sweep_fast_kernel(FastArgs a) {
   s.vcol = (double*)(smem + off[6]);
   s.binom = (uint64_t*)(smem + off[7]);
   s.cmax = (uint32_t*)(smem + off[13]);
+  s.c4 = (uint2*)(smem + off[14]);
   s.tk.top = (Rec*)(smem + off[8]);
   s.tk.cand = (Rec*)(smem + off[9]);
   s.tk.tmp = (Rec*)(smem + off[10]);
@@ -306,9 +385,14 @@ __global__ void __launch_bounds__(FAST_BD, 4) sweep_fast_kernel(FastArgs a) {
       uint64_t v = ld16(B, col + (c >> 2) * 8 + (c & 3) * 2) >> LAT_SHIFT;
       c1 += v;
       c2 += v * v;
-      if constexpr (TAIL) cm = max(cm, (uint32_t)v);
+      if constexpr (TAIL == FAST_MAX) cm = max(cm, (uint32_t)v);
     }
-    if constexpr (TAIL) s.cmax[i] = cm;
+    if constexpr (TAIL == FAST_MAX) s.cmax[i] = cm;
+    if constexpr (TAIL == FAST_LIST) {  // (a pass of its own: once per block)
+      uint32_t cl[PCTL_FAST_DEPTH] = {0, 0, 0, 0};
+      for (uint32_t c = 0; c < a.nc; ++c) list_insert(cl, ld16(B, col + (c >> 2) * 8 + (c & 3) * 2) >> LAT_SHIFT);
+      s.c4[i] = make_uint2(cl[0] | (cl[1] << 16), cl[2] | (cl[3] << 16));
+    }
     s.cs1[i] = (uint32_t)c1;
     s.cs2[i] = c2;
     s.vcol[i] = (double)((uint64_t)a.nc * c2 - c1 * c1);  // exact: < 2^53
@@ -355,7 +439,7 @@ __global__ void __launch_bounds__(FAST_BD, 4) sweep_fast_kernel(FastArgs a) {
         // ---- Q phase: sorted off-diagonal distances of each member's row
         uint32_t Q2[N], Q3[N];
         uint32_t cS1[NL], cS2[NL];
-        uint32_t cMX[NL];  // TAIL: the colocated leaderless maxima
+        uint32_t cMX[NL];  // FAST_MAX: the colocated leaderless maxima
 #pragma unroll
         for (int t = 0; t < NL; ++t) cS1[t] = cS2[t] = cMX[t] = 0;
 #pragma unroll
@@ -383,7 +467,7 @@ __global__ void __launch_bounds__(FAST_BD, 4) sweep_fast_kernel(FastArgs a) {
             ql[t2] = v[QC::lq(t2) - 2];
             cS1[t2] += ql[t2];
             cS2[t2] += ql[t2] * ql[t2];
-            if constexpr (TAIL) cMX[t2] = max(cMX[t2], ql[t2]);
+            if constexpr (TAIL == FAST_MAX) cMX[t2] = max(cMX[t2], ql[t2]);
           }
           *(uint32_t*)(smem + qlane + ((uint32_t)j << QSH)) = ql[0] | (NL >= 2 ? ql[NL >= 2 ? 1 : 0] << 16 : 0u);
           if (NL == 3) *(uint32_t*)(smem + qlane + ((uint32_t)(N + j) << QSH)) = ql[NL - 1];
@@ -427,14 +511,16 @@ __global__ void __launch_bounds__(FAST_BD, 4) sweep_fast_kernel(FastArgs a) {
         }
         if (have) {
           Mom mom[NSLOT];
-          uint32_t mx[NSLOT];  // TAIL: the slots' maxima
+          uint32_t mx[NSLOT];     // FAST_MAX: the slots' maxima
+          uint32_t l4[NSLOT][2];  // FAST_LIST: the slots' four largest values, packed (FPaxos: less the quorum latency)
           // Input leaderless: the hot loop (first, so little is live across it)
           {
             uint32_t S1[NL];
             uint64_t S2[NL];
             uint32_t MX[NL];
+            uint32_t ML[NL][2];
             client_quads<N, NL, TAIL>(B, s.cqt, ABLATE(a, 1) ? 0u : nq, ABLATE(a, 1) ? 0u : rem, a.s2_flush, colT,
-                                      qlane, S1, S2, MX);
+                                      qlane, S1, S2, MX, ML);
             if (ABLATE(a, 1)) {  // timing only: non-degenerate dummy sums (nothing defers)
 #pragma unroll
               for (int t = 0; t < NL; ++t) {
@@ -445,29 +531,42 @@ __global__ void __launch_bounds__(FAST_BD, 4) sweep_fast_kernel(FastArgs a) {
             mom[SLOT_AF1] = Mom{S1[QC::idx_a1], S2[QC::idx_a1], nc};
             mom[SLOT_AF2] = Mom{S1[QC::idx_a2], S2[QC::idx_a2], nc};
             mom[SLOT_E] = Mom{S1[QC::idx_e], S2[QC::idx_e], nc};
-            if constexpr (TAIL) {
+            if constexpr (TAIL == FAST_MAX) {
               mx[SLOT_AF1] = MX[QC::idx_a1];
               mx[SLOT_AF2] = MX[QC::idx_a2];
               mx[SLOT_E] = MX[QC::idx_e];
+            }
+            if constexpr (TAIL == FAST_LIST) {
+#pragma unroll
+              for (int h = 0; h < 2; ++h) {
+                l4[SLOT_AF1][h] = ML[QC::idx_a1][h];
+                l4[SLOT_AF2][h] = ML[QC::idx_a2][h];
+                l4[SLOT_E][h] = ML[QC::idx_e][h];
+              }
             }
           }
           // Input FPaxos: moments from the leader column's sums
           mom[SLOT_FF1] = leader_mom(s.cs1[lp], s.cs2[lp], nc, lq2);
           mom[SLOT_FF2] = leader_mom(s.cs1[lp], s.cs2[lp], nc, lq3);
-          if constexpr (TAIL) {
+          if constexpr (TAIL == FAST_MAX) {
             const uint32_t cm = s.cmax[lp];
             mx[SLOT_FF1] = cm + lq2;
             mx[SLOT_FF2] = cm + lq3;
+          }
+          if constexpr (TAIL == FAST_LIST) {
+            const uint2 c = s.c4[lp];
+            l4[SLOT_FF1][0] = l4[SLOT_FF2][0] = c.x;
+            l4[SLOT_FF1][1] = l4[SLOT_FF2][1] = c.y;
           }
           // Colocated: leaderless values are the members' own quorum latencies;
           // FPaxos reads the leader's column of the config submatrix.
           {
             uint32_t f1 = 0, f1s = 0, f2 = 0, f2s = 0;
-            uint32_t fm = 0;  // TAIL: the members' largest latency to the leader
+            uint32_t fm = 0;  // FAST_MAX: the members' largest latency to the leader
 #pragma unroll
             for (int k = 0; k < N; ++k) {
               const uint32_t v = ld16(B, lcol + rowq[k]) >> LAT_SHIFT;
-              if constexpr (TAIL) fm = max(fm, v);
+              if constexpr (TAIL == FAST_MAX) fm = max(fm, v);
               const uint32_t x1 = v + lq2, x2 = v + lq3;
               f1 += x1;
               f1s += x1 * x1;
@@ -479,15 +578,65 @@ __global__ void __launch_bounds__(FAST_BD, 4) sweep_fast_kernel(FastArgs a) {
             mom[5 + SLOT_AF1] = Mom{cS1[QC::idx_a1], cS2[QC::idx_a1], (uint32_t)N};
             mom[5 + SLOT_AF2] = Mom{cS1[QC::idx_a2], cS2[QC::idx_a2], (uint32_t)N};
             mom[5 + SLOT_E] = Mom{cS1[QC::idx_e], cS2[QC::idx_e], (uint32_t)N};
-            if constexpr (TAIL) {
+            if constexpr (TAIL == FAST_MAX) {
               mx[5 + SLOT_FF1] = fm + lq2;
               mx[5 + SLOT_FF2] = fm + lq3;
               mx[5 + SLOT_AF1] = cMX[QC::idx_a1];
               mx[5 + SLOT_AF2] = cMX[QC::idx_a2];
               mx[5 + SLOT_E] = cMX[QC::idx_e];
             }
+            if constexpr (TAIL == FAST_LIST) {
+              // the members' four largest latencies to the leader (the N-step loop's values again)
+              uint32_t fl[PCTL_FAST_DEPTH] = {0, 0, 0, 0};
+#pragma unroll
+              for (int k = 0; k < N; ++k) list_insert(fl, ld16(B, lcol + rowq[k]) >> LAT_SHIFT);
+              l4[5 + SLOT_FF1][0] = l4[5 + SLOT_FF2][0] = fl[0] | (fl[1] << 16);
+              l4[5 + SLOT_FF1][1] = l4[5 + SLOT_FF2][1] = fl[2] | (fl[3] << 16);
+              // the members' own quorum latencies, read back from the lane's
+              // qtab planes: word j holds tables 0 and 1, word N + j table 2
+              us2 pa[PCTL_FAST_DEPTH], pb[PCTL_FAST_DEPTH];
+#pragma unroll
+              for (int i = 0; i < PCTL_FAST_DEPTH; ++i) pa[i] = pb[i] = us2{0, 0};
+#pragma unroll
+              for (int j = 0; j < N; ++j) {
+                pk_insert(pa, as_us2(ld32(B, qlane + ((uint32_t)j << QSH))));
+                if (NL == 3) pk_insert(pb, as_us2(ld32(B, qlane + ((uint32_t)(N + j) << QSH))));
+              }
+              uint32_t cl[3][2];
+#pragma unroll
+              for (int h = 0; h < 2; ++h) {
+                cl[0][h] = (uint32_t)pa[2 * h].x | ((uint32_t)pa[2 * h + 1].x << 16);
+                cl[1][h] = (uint32_t)pa[2 * h].y | ((uint32_t)pa[2 * h + 1].y << 16);
+                cl[2][h] = (uint32_t)pb[2 * h].x | ((uint32_t)pb[2 * h + 1].x << 16);
+                l4[5 + SLOT_AF1][h] = cl[QC::idx_a1][h];
+                l4[5 + SLOT_AF2][h] = cl[QC::idx_a2][h];
+                l4[5 + SLOT_E][h] = cl[QC::idx_e][h];
+              }
+            }
           }
-          if constexpr (TAIL) {
+          if constexpr (TAIL == FAST_LIST) {
+            // the MAX and percentile keys first, as below for FAST_MAX
+#pragma unroll
+            for (int o = 0; o < MAXOBJ; ++o) {
+              if (o >= a.n_obj) break;
+              const uint32_t kind = a.obj_kind[o];
+              if (kind < OBJ_MAX) continue;
+              const uint32_t sl = a.obj_slot[o];
+              const bool pctl = kind >= OBJ_PCTL;
+              const uint32_t need = pctl ? kind & PCTL_NEED_MASK : 1u;  // (MAX: the first entry)
+              const bool whole = pctl && (kind & PCTL_WHOLE);
+#pragma unroll
+              for (int q = 0; q < NSLOT; ++q) {
+                if ((uint32_t)q != sl) continue;
+                const uint32_t add = q % 5 == SLOT_FF1 ? lq2 : q % 5 == SLOT_FF2 ? lq3 : 0u;
+                const uint32_t v = list_at(l4[q], need) + add;
+                const uint32_t twice = whole ? v + list_at(l4[q], need - 1) + add : 2 * v;
+                ok[o] = true;
+                key[o] = pctl ? pctl_key(twice, mom[q].s1) : max_key(v, mom[q].s1);
+              }
+            }
+          }
+          if constexpr (TAIL == FAST_MAX) {
             // the MAX keys first (the maxima die here, before the score and
             // digest arithmetic); a deferred config withdraws them below
 #pragma unroll
@@ -530,10 +679,13 @@ __global__ void __launch_bounds__(FAST_BD, 4) sweep_fast_kernel(FastArgs a) {
 // ------------------------------------------------------------- launcher ---
 // the kernel for config size n (null: unsupported), for the occupancy query
 // and the launch alike
-static const void* fast_fn(uint32_t n, bool tail) {
+static const void* fast_fn(uint32_t n, int tail) {
   switch (n) {
-#define FN_CASE(NN) \
-  case NN: return tail ? (const void*)sweep_fast_kernel<NN, true> : (const void*)sweep_fast_kernel<NN, false>;
+#define FN_CASE(NN)                                                                  \
+  case NN:                                                                           \
+    return tail == FAST_LIST  ? (const void*)sweep_fast_kernel<NN, FAST_LIST>        \
+           : tail == FAST_MAX ? (const void*)sweep_fast_kernel<NN, FAST_MAX>         \
+                              : (const void*)sweep_fast_kernel<NN, FAST_PLAIN>;
     FN_CASE(2) FN_CASE(3) FN_CASE(4) FN_CASE(5) FN_CASE(6) FN_CASE(7) FN_CASE(8) FN_CASE(9)
     FN_CASE(10) FN_CASE(11) FN_CASE(12) FN_CASE(13) FN_CASE(14) FN_CASE(15) FN_CASE(16)
 #undef FN_CASE
@@ -541,12 +693,12 @@ static const void* fast_fn(uint32_t n, bool tail) {
   }
 }
 
-int fast_occupancy(uint32_t n, bool tail, size_t shm) {
+int fast_occupancy(uint32_t n, int tail, size_t shm) {
   const void* k = fast_fn(n, tail);
   return k ? kernel_occupancy(k, FAST_BD, shm, 1) : 0;
 }
 
-hipError_t launch_fast(const FastArgs& a, uint32_t n, bool tail, uint32_t grid, size_t shm, hipStream_t st,
+hipError_t launch_fast(const FastArgs& a, uint32_t n, int tail, uint32_t grid, size_t shm, hipStream_t st,
                        hipEvent_t e0, hipEvent_t e1) {
   const void* k = fast_fn(n, tail);
   return k ? launch_kernel(k, a, grid, FAST_BD, shm, st, e0, e1) : hipErrorInvalidValue;

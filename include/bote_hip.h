@@ -93,6 +93,14 @@ extern "C" {
 /* min Histogram::max of `slot` (histogram.rs:102-108: the worst client), then
  * min mean among the configs sharing it.  Kinds 3..15 are not defined. */
 #define BOTE_OBJ_MAX 16
+/* min Histogram::percentile(p) of `slot` (histogram.rs:110-170, the p95, p99,
+ * ... of fantoch's stats_fmt), then min mean.  `bp` is the percentile in
+ * 1/10,000 (p95 = 9500, p99.9 = 9990), 1 <= bp <= 9999, and p = bp / 10000.0
+ * (one f64 division: the double a Rust literal such as 0.95 denotes).  A kind
+ * is a percentile iff (kind >> 16) == 1 and its low half is in 1..9999; a
+ * percentile that needs more than 8 of the slot's largest values
+ * (bote_percentile_index) is BOTE_E_RANGE. */
+#define BOTE_OBJ_PCTL(bp) (0x10000u | (bp))
 
 /* Sweep kernel paths (bote_sweep_create_ex); every path is exact. */
 #define BOTE_KERNEL_AUTO 0    /* group kernel when eligible, else fast, else generic */
@@ -131,6 +139,12 @@ typedef struct {
  *          over the n members for the colocated slots), then its exact sum
  *          (the MEAN key).  Both fit: a value is a latency plus a quorum
  *          latency, max <= 2 * 16383, and S1 <= 4096 * 2 * 16383 < 2^27.
+ *   PCTL:  key = (T << 32) | S1 with T = 2 * Histogram::percentile(p), an exact
+ *          integer, over the same values as MAX.  With the slot's `c` values
+ *          ascending s[0..c), x = p * c (one f64 multiply), idx = round(x)
+ *          (half away from zero) and whole = (x - idx == 0.0): T = 2 s[0] when
+ *          idx == 0, s[idx-1] + s[idx] when whole, else 2 s[idx-1]
+ *          (bote_percentile_index gives idx and whole).  T <= 4 * 16383.
  * rank = colex rank of the config: rank = sum_j C(p_j, j+1), p ascending
  * positions into the server list. */
 typedef struct {
@@ -268,7 +282,12 @@ int bote_sweep_create(const bote_planet* p, const uint32_t* servers, uint32_t ns
  * fast/group path that the planet or lists do not qualify for is BOTE_E_ARG.
  * A BOTE_OBJ_MAX objective runs on the fast kernel's worst-client variant
  * (AUTO, base key set, eligible planet) or the generic kernel; the group
- * kernel does not compute it, so a forced BOTE_KERNEL_GROUP is BOTE_E_ARG. */
+ * kernel does not compute it, so a forced BOTE_KERNEL_GROUP is BOTE_E_ARG.
+ * A BOTE_OBJ_PCTL objective needs the c - max(idx, 1) + 1 largest values of
+ * its slot: up to 4 run on the fast kernel's sorted-list variant (AUTO or
+ * forced fast, base key set, eligible planet), 5..8 on the generic kernel
+ * (a forced fast kernel is BOTE_E_ARG), as do the extended key set and
+ * ineligible planets; a forced group kernel is BOTE_E_ARG as for MAX. */
 int bote_sweep_create_ex(const bote_planet* p, const uint32_t* servers, uint32_t ns,
                          const uint32_t* clients, uint32_t nc, uint32_t n,
                          const bote_objective* objs, uint32_t n_obj, uint32_t K,
@@ -377,6 +396,11 @@ int bote_search_topk(const bote_planet* const* planets, uint32_t n_devices,
 int bote_colex_unrank(uint64_t rank, uint32_t n, uint32_t ns, uint32_t* out_positions);
 /* C(ns, n) as uint64 (0 on overflow or n > ns). */
 uint64_t bote_binomial(uint32_t ns, uint32_t n);
+/* Histogram::percentile's index arithmetic for p = bp / 10000.0 over `count`
+ * values (host only): *out_idx = round(p * count), *out_whole = 1 when
+ * p * count is that integer exactly (the percentile is then the midpoint of
+ * s[idx-1] and s[idx]).  BOTE_E_ARG unless 1 <= bp <= 9999 and count >= 1. */
+int bote_percentile_index(uint32_t bp, uint32_t count, uint32_t* out_idx, int* out_whole);
 
 #ifdef __cplusplus
 }

@@ -34,6 +34,11 @@ pub const BOTE_OBJ_MEAN: u32 = 1;
 pub const BOTE_OBJ_COV: u32 = 2;
 /// min worst client of a slot, then min sum: key = (max << 32) | sum
 pub const BOTE_OBJ_MAX: u32 = 16;
+/// min Histogram::percentile(bp / 10000.0) of a slot (p95 = 9500), then min sum:
+/// key = (2 * percentile << 32) | sum; 1 <= bp <= 9999
+pub const fn bote_obj_pctl(bp: u32) -> u32 {
+    0x10000 | bp
+}
 
 #[repr(C)]
 pub struct bote_planet {
@@ -142,6 +147,7 @@ extern "C" {
     pub fn bote_sweep_destroy(s: *mut bote_sweep) -> c_int;
     pub fn bote_colex_unrank(rank: u64, n: u32, ns: u32, out_positions: *mut u32) -> c_int;
     pub fn bote_binomial(ns: u32, n: u32) -> u64;
+    pub fn bote_percentile_index(bp: u32, count: u32, out_idx: *mut u32, out_whole: *mut c_int) -> c_int;
 }
 
 /// Turns a status code into the panic the reference raises at the same place
