@@ -34,6 +34,10 @@ NSLOTS_X = 20
 SLOT_NAMES_X = SLOT_NAMES + ["ttf1", "ttf2", "twf1", "twf2", "ttf1C", "ttf2C", "twf1C", "twf2C", "fl1", "fl2"]
 OBJ_SCORE, OBJ_MEAN, OBJ_COV = 0, 1, 2
 OBJ_MAX = 16  # the slot's worst client, then its sum: key = max << 32 | sum (bote.max_key)
+# the slot's mean distance to its mean, then its sum: key = H << 27 | sum with
+# H = sum over the values above the mean of (count * x - sum) (bote.mdtm_key)
+OBJ_MDTM = 18
+MDTM_SUM_BITS = 27
 FT_F1, FT_F1F2 = 1, 2
 KP = 128
 

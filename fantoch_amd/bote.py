@@ -712,6 +712,14 @@ def pctl_key(key: int) -> Tuple[int, int]:
     return int(key) >> 32, int(key) & 0xFFFFFFFF
 
 
+def mdtm_key(key: int) -> Tuple[int, int]:
+    """(H, sum) of an OBJ_MDTM record's key: H = the sum over the slot's values
+    above its mean of (count * x - sum), half the exact sum of |count * x - sum|,
+    in the bits above the low 27; the slot's exact sum (the OBJ_MEAN key) in the
+    low 27.  Histogram::mdtm (histogram.rs:221-235) is 2 * H / count**2."""
+    return int(key) >> _lib.MDTM_SUM_BITS, int(key) & ((1 << _lib.MDTM_SUM_BITS) - 1)
+
+
 def pctl_kind(p: float) -> int:
     """The objective kind of percentile `p` (0.95 -> _lib.OBJ_PCTL(9500)); p must be
     a multiple of 0.0001 in 0.0001 .. 0.9999."""

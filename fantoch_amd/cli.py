@@ -18,7 +18,7 @@ main.rs:31-60).  Subcommands expose them, and the sweep the hot path serves:
   python -m fantoch_amd distance-table [--lat-dir D] [--regions a,b,...]
   python -m fantoch_amd stats --config a,b,c [--clients ...] [--tempo] [--lat-dir D]
   python -m fantoch_amd sweep (--synthetic R [--seed S] | --lat-dir D) --n N [--K 100]
-                        [--objectives default|config5|mean:af1,cov:af1,max:af1,p95:af1,p99.9:e,score,...]
+                        [--objectives default|config5|mean:af1,cov:af1,max:af1,p95:af1,p99.9:e,mdtm:af1,score,...]
                         [--keys base|tempo-all-leaders] [--gpus G] [--rank-begin B --rank-end E]
 """
 from __future__ import annotations
@@ -129,7 +129,8 @@ def _objective_name(kind: int) -> str:
     if _lib.is_pctl(kind):
         whole, frac = divmod(kind & 0xFFFF, 100)
         return f"p{whole}" + (f".{frac:02d}".rstrip("0") if frac else "")
-    return {_lib.OBJ_SCORE: "score", _lib.OBJ_MEAN: "mean", _lib.OBJ_COV: "cov", _lib.OBJ_MAX: "max"}[kind]
+    return {_lib.OBJ_SCORE: "score", _lib.OBJ_MEAN: "mean", _lib.OBJ_COV: "cov", _lib.OBJ_MAX: "max",
+            _lib.OBJ_MDTM: "mdtm"}[kind]
 
 
 def _objectives(spec: str):
@@ -140,7 +141,8 @@ def _objectives(spec: str):
         return list(DEFAULT_OBJECTIVES)
     if spec == "config5":
         return list(CONFIG5_OBJECTIVES)
-    kinds = {"score": _lib.OBJ_SCORE, "mean": _lib.OBJ_MEAN, "cov": _lib.OBJ_COV, "max": _lib.OBJ_MAX}
+    kinds = {"score": _lib.OBJ_SCORE, "mean": _lib.OBJ_MEAN, "cov": _lib.OBJ_COV, "max": _lib.OBJ_MAX,
+             "mdtm": _lib.OBJ_MDTM}
     out = []
     for item in spec.split(","):
         if item == "score":
@@ -160,7 +162,7 @@ def sweep(args, out=sys.stdout) -> dict:
     import numpy as np
 
     from . import _lib
-    from .bote import DEFAULT_RANKING, DevicePlanet, MultiDeviceSearch, Sweep, max_key, pctl_key
+    from .bote import DEFAULT_RANKING, DevicePlanet, MultiDeviceSearch, Sweep, max_key, mdtm_key, pctl_key
 
     planet = _planet(args)
     srv = np.arange(planet.R, dtype=np.uint32)
@@ -184,7 +186,7 @@ def sweep(args, out=sys.stdout) -> dict:
     def regions(rank):
         return [planet.names[i] for i in _lib.colex_unrank(int(rank), args.n, planet.R)]
 
-    def record(kind, key, rank):
+    def record(kind, slot, key, rank):
         rec = {"key": str(key), "rank": rank, "regions": regions(rank)}
         if kind == _lib.OBJ_MAX:  # the composite key's halves
             rec["max"], rec["sum"] = max_key(key)
@@ -192,12 +194,16 @@ def sweep(args, out=sys.stdout) -> dict:
             twice, rec["sum"] = pctl_key(key)
             rec["percentile"] = twice / 2
             rec = {k: rec[k] for k in ("key", "rank", "regions", "percentile", "sum")}
+        elif kind == _lib.OBJ_MDTM:  # Histogram::mdtm = 2 H / count^2 (count: the clients, or n for a colocated slot)
+            h, total = mdtm_key(key)
+            count = args.n if 5 <= slot < 10 or 14 <= slot < 18 else planet.R
+            rec["mdtm"], rec["sum"] = 2 * h / count ** 2, total
         return rec
 
     doc = {"regions": planet.R, "n": args.n, "rank_begin": rb, "rank_end": re, "configs": re - rb,
            "keys": args.keys, "gpus": args.gpus, "valid": res.valid, "digest": str(res.digest),
            "objectives": [{"objective": _objective_name(k) + ("" if k == _lib.OBJ_SCORE else ":" + _lib.SLOT_NAMES_X[s]),
-                           "top": [record(k, key, rank) for key, rank in res.tops[o][:args.show]]}
+                           "top": [record(k, s, key, rank) for key, rank in res.tops[o][:args.show]]}
                           for o, (k, s) in enumerate(objs)]}
     print(json.dumps(doc, indent=None if args.compact else 1), file=out)
     return doc

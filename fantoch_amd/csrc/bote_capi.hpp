@@ -192,7 +192,7 @@ struct bote_sweep {
   bool launched = false;
   Path path = Path::Generic;
   bool def_obj = false;  // the default objective set, compiled into the group kernel
-  int tail = 0;          // bote::FAST_*: a MAX or percentile objective picks the fast kernel's variant (never the group kernel)
+  int tail = 0;          // bote::FAST_*: a MAX, percentile or MDTM objective picks the fast kernel's variant (never the group kernel)
   bote::FastArgs fargs{};  // fast and group kernels
   uint32_t fgrid = 0;
   size_t fshm = 0;

@@ -101,9 +101,7 @@ static int sweep_upload_lists(bote_sweep* s, const uint32_t* servers, const uint
   s->shm = bote::eval_smem_bytes(a, n, s->bd, true);
   a.out_top = nullptr;
   if (s->shm > device_max_lds(p->device)) return fail(BOTE_E_RANGE, "planet/client set too large for LDS");
-  bool pctl = false;
-  for (uint32_t o = 0; o < n_obj; ++o) pctl = pctl || a.obj_kind[o] >= bote::OBJ_PCTL;
-  int nb = bote::eval_occupancy(n, false, s->bd, s->shm, keys != 0, pctl);
+  int nb = bote::eval_occupancy(n, false, s->bd, s->shm, keys != 0, bote::eval_passes(a.obj_kind, (int)n_obj));
   s->grid = (uint32_t)(device_cus(p->device) * nb);
   s->xgrid = 32;
   return BOTE_OK;
@@ -173,8 +171,8 @@ static int sweep_plan_group(bote_sweep* s, const FastLimits& lim, bool compiled_
   const bote_planet* p = s->p;
   const uint32_t n = s->n, ns = s->ns, nc = s->nc;
   bote::FastArgs& f = s->fargs;
-  // (a MAX objective: the fast kernel's TAIL variant; a forced group kernel
-  // was refused with the arguments, check_sweep_args)
+  // (a MAX, percentile or MDTM objective: the fast kernel's variant, s->tail; a
+  // forced group kernel was refused with the arguments, check_sweep_args)
   bool want_group = n >= 4 && ns <= 256 && group_utilisation(ns, n) >= 0.9 && !s->tail;
   if (kernel != BOTE_KERNEL_AUTO) want_group = n >= 4 && ns <= 256 && kernel == BOTE_KERNEL_GROUP;
   if (kernel == BOTE_KERNEL_GROUP && !want_group) return fail(BOTE_E_ARG, "group kernel needs n >= 4");
@@ -300,15 +298,22 @@ static int sweep_plan_fast(bote_sweep* s, const uint32_t* servers, const uint32_
   // a MAX objective: the worst-client variant of the fast kernel (base key
   // set), else the generic kernel; a percentile objective: its list variant
   // when every one needs at most PCTL_FAST_DEPTH values, else the generic kernel
+  // an MDTM objective: the fast kernel's MDTM variant (base key set), which
+  // carries no maxima or lists, so with a MAX or percentile objective beside
+  // it the generic kernel
   s->tail = bote::FAST_PLAIN;
   uint32_t need = 0;
+  bool mdtm = false;
   for (uint32_t o = 0; o < s->n_obj; ++o) {
     if (a.obj_kind[o] == BOTE_OBJ_MAX) s->tail = std::max(s->tail, (int)bote::FAST_MAX);
     if (a.obj_kind[o] >= bote::OBJ_PCTL) {
       s->tail = bote::FAST_LIST;
       need = std::max(need, a.obj_kind[o] & bote::PCTL_NEED_MASK);
     }
+    mdtm = mdtm || a.obj_kind[o] == BOTE_OBJ_MDTM;
   }
+  const bool mdtm_mixed = mdtm && s->tail != bote::FAST_PLAIN;
+  if (mdtm) s->tail = bote::FAST_MDTM;
   const FastLimits lim = fast_limits(p->lat.data(), p->R, nc, n);
   if (keys && eligible &&
       (!bote::group_supports_keys(n, bote::GROUP_XK_MAX_BD) || !compiled_objs || !lim.keys32 ||
@@ -322,6 +327,12 @@ static int sweep_plan_fast(bote_sweep* s, const uint32_t* servers, const uint32_
     if (kernel == BOTE_KERNEL_FAST)
       return fail(BOTE_E_ARG, "the fast kernel's percentile lists are 4 deep: an objective needs " +
                                   std::to_string(need) + " of its slot's largest values (generic kernel)");
+    s->path = Path::Generic;
+  }
+  if (mdtm_mixed && s->path != Path::Generic) {
+    if (kernel == BOTE_KERNEL_FAST)
+      return fail(BOTE_E_ARG, "the fast kernel's MDTM variant carries no maxima or lists: a sweep with MDTM and MAX or "
+                              "percentile objectives runs the generic kernel, which computes both");
     s->path = Path::Generic;
   }
   if (s->path == Path::Generic) return BOTE_OK;

@@ -296,6 +296,29 @@ __device__ __forceinline__ uint64_t max_key(uint32_t mx, uint64_t s1) { return (
 // Percentile objective key (BOTE_OBJ_PCTL): twice the percentile (an exact
 // integer <= 4 * 16383), then the slot's exact sum.
 __device__ __forceinline__ uint64_t pctl_key(uint32_t twice, uint64_t s1) { return ((uint64_t)twice << 32) | s1; }
+// MDTM objective key (BOTE_OBJ_MDTM): H = the sum over the slot's values above
+// its mean of (cnt * x - S1), half the exact sum of |cnt * x - S1|, then the
+// slot's exact sum.  Histogram::mdtm (histogram.rs:221-235) is 2 H / cnt^2.
+constexpr int MDTM_SUM_BITS = 27;
+constexpr uint64_t MDTM_MAX_CNT = 4096, MDTM_MAX_VAL = 2 * 16383;  // clients; a slot's largest value
+static_assert(MDTM_MAX_CNT * MDTM_MAX_VAL < (1ull << MDTM_SUM_BITS) - 1, "S1 fits its field, and the key is never all ones");
+// (the mean absolute deviation is at most half the range: 2 H <= cnt^2 * max / 2)
+static_assert(MDTM_MAX_CNT * MDTM_MAX_CNT * MDTM_MAX_VAL / 4 < (1ull << (64 - MDTM_SUM_BITS)), "H fits above S1");
+__device__ __forceinline__ uint64_t mdtm_key(uint64_t h, uint64_t s1) { return (h << MDTM_SUM_BITS) | s1; }
+// The threshold of a slot with count cnt and sum s1: T = floor(s1 / cnt) (x >
+// T is exactly cnt * x > s1 for integers; a value at an integral mean is not
+// above it) and r = s1 - cnt * T.  Then with A = the sum of max(x - T, 0) and
+// B = the number of x > T:  H = cnt * A - r * B.
+struct MdtmThr {
+  uint32_t T, r;
+};
+__device__ __forceinline__ MdtmThr mdtm_thr(uint32_t s1, uint32_t cnt) {
+  const uint32_t T = s1 / cnt;  // (exact integer division)
+  return MdtmThr{T, s1 - T * cnt};
+}
+__device__ __forceinline__ uint64_t mdtm_h(uint32_t cnt, MdtmThr t, uint32_t A, uint32_t B) {
+  return (uint64_t)cnt * A - (uint64_t)t.r * B;
+}
 
 // Per-config digest, summed over configs mod 2^64.  A linear
 // fold of 32-bit words, each times its own constant as two 16-bit halves (one

@@ -29,8 +29,9 @@ __device__ __forceinline__ void defer_rank(const FastArgs& a, uint64_t rank) {
 // the config and offers nothing to the top-K.  TAIL (the fast kernel's
 // variant, FAST_*): with FAST_MAX a MAX objective's key and ok are left as
 // the caller, which holds the slots' maxima, set them; with FAST_LIST a MAX or
-// percentile objective's, from the caller's sorted lists; with FAST_PLAIN no
-// objective has those kinds.
+// percentile objective's, from the caller's sorted lists; with FAST_MDTM an
+// MDTM objective's, from the caller's second pass (such a sweep has no MAX or
+// percentile objective); with FAST_PLAIN no objective has those kinds.
 template <int N, int TAIL = FAST_PLAIN>
 __device__ __forceinline__ bool finish_config(const FastArgs& a, const Mom (&mom)[NSLOT], double vcol_lead,
                                               uint32_t lead_member, uint64_t rank, const Rec* thr, double pnc1,
@@ -129,6 +130,7 @@ __device__ __forceinline__ bool finish_config(const FastArgs& a, const Mom (&mom
     }
     if (TAIL == FAST_MAX && kind == OBJ_MAX) continue;
     if (TAIL == FAST_LIST && kind >= OBJ_MAX) continue;
+    if (TAIL == FAST_MDTM && kind == OBJ_MDTM) continue;
 #pragma unroll
     for (int q = 0; q < NSLOT; ++q) {
       if ((uint32_t)q != sl) continue;

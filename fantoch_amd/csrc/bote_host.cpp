@@ -422,6 +422,20 @@ uint32_t percentile_need(uint32_t bp, uint32_t count) {
   return count - std::max(idx, 1u) + 1;
 }
 
+uint64_t mdtm_half_deviation(const uint32_t* x, uint32_t c) {
+  uint64_t s1 = 0, h = 0;
+  for (uint32_t i = 0; i < c; ++i) s1 += x[i];
+  for (uint32_t i = 0; i < c; ++i)
+    if ((uint64_t)c * x[i] > s1) h += (uint64_t)c * x[i] - s1;
+  return h;
+}
+
+bool mdtm_key(uint64_t H, uint64_t S1, uint64_t& key) {
+  if (S1 >= (1ull << MDTM_SUM_BITS) - 1 || H >= (1ull << (64 - MDTM_SUM_BITS))) return false;
+  key = (H << MDTM_SUM_BITS) | S1;
+  return true;
+}
+
 bool chunk_states(const uint64_t* starts, uint32_t count, uint32_t n, uint32_t ns, std::vector<uint64_t>& out) {
   const uint32_t F = n - 3;
   out.assign((size_t)count * 4, 0);
@@ -633,10 +647,10 @@ Status check_sweep_args(uint32_t R, const uint32_t* servers, uint32_t ns, const 
   if (n_obj > BOTE_MAX_OBJECTIVES) return fail(BOTE_E_RANGE, "more than 8 objectives");
   if (n_obj && !objs) return fail(BOTE_E_ARG, "objectives null");
   if (K == 0 || K > BOTE_MAX_K) return fail(BOTE_E_RANGE, "K must be in [1, 128]");
-  bool has_max = false, has_pctl = false;
+  bool has_max = false, has_pctl = false, has_mdtm = false;
   for (uint32_t o = 0; o < n_obj; ++o) {
     const bool pctl = is_percentile_kind(objs[o].kind);
-    if (objs[o].kind > BOTE_OBJ_COV && objs[o].kind != BOTE_OBJ_MAX && !pctl)
+    if (objs[o].kind > BOTE_OBJ_COV && objs[o].kind != BOTE_OBJ_MAX && objs[o].kind != BOTE_OBJ_MDTM && !pctl)
       return fail(BOTE_E_ARG, "unknown objective kind");
     if (objs[o].kind == BOTE_OBJ_SCORE) {
       has_score = true;
@@ -645,6 +659,7 @@ Status check_sweep_args(uint32_t R, const uint32_t* servers, uint32_t ns, const 
     if (objs[o].slot >= (keys ? BOTE_NSLOTS_X : BOTE_NSLOTS)) return fail(BOTE_E_ARG, "slot out of range");
     if (!slot_exists_n(n, objs[o].slot, keys)) return fail(BOTE_E_ARG, "slot does not exist for this n (max_f < 2)");
     has_max = has_max || objs[o].kind == BOTE_OBJ_MAX;
+    has_mdtm = has_mdtm || objs[o].kind == BOTE_OBJ_MDTM;
     if (pctl) {
       has_pctl = true;
       if (percentile_need(objs[o].kind & 0xFFFF, slot_count(objs[o].slot, nc, n)) > PCTL_MAX_NEED)
@@ -656,6 +671,8 @@ Status check_sweep_args(uint32_t R, const uint32_t* servers, uint32_t ns, const 
     return fail(BOTE_E_ARG, "the group kernel does not compute MAX objectives (fast or generic kernel)");
   if (has_pctl && kernel == BOTE_KERNEL_GROUP)
     return fail(BOTE_E_ARG, "the group kernel does not compute percentile objectives (fast or generic kernel)");
+  if (has_mdtm && kernel == BOTE_KERNEL_GROUP)
+    return fail(BOTE_E_ARG, "the group kernel does not compute MDTM objectives (fast or generic kernel)");
   if (has_score && !rp) return fail(BOTE_E_ARG, "SCORE objective needs ranking params");
   if (rp) return check_ft_metric(rp->ft_metric);
   return OK;

@@ -156,6 +156,21 @@ bool percentile_index(uint32_t bp, uint32_t count, uint32_t& idx, bool& whole);
 // that one and the (need - 1)-th largest.  0 for bad arguments.
 uint32_t percentile_need(uint32_t bp, uint32_t count);
 
+// ----------------------------------------------------- MDTM objectives --
+// BOTE_OBJ_MDTM's key is (H << MDTM_SUM_BITS) | S1 (include/bote_hip.h).  Both
+// halves fit for every slot the library admits: at most BOTE_MAX_CLIENTS
+// values of at most 2 * 16383 each, and a mean absolute deviation of at most
+// half the range (2 H <= c^2 * max / 2).  S1 < 2^27 - 1, so no key is all ones.
+constexpr uint32_t MDTM_SUM_BITS = BOTE_MDTM_SUM_BITS;
+constexpr uint64_t MDTM_MAX_VALUE = 2 * 16383;
+static_assert((uint64_t)BOTE_MAX_CLIENTS * MDTM_MAX_VALUE < (1ull << MDTM_SUM_BITS) - 1, "S1 fits its field");
+static_assert((uint64_t)BOTE_MAX_CLIENTS * BOTE_MAX_CLIENTS * MDTM_MAX_VALUE / 4 < (1ull << (64 - MDTM_SUM_BITS)),
+              "H fits above S1");
+// H by its definition: the sum over { i : c x_i > S1 } of (c x_i - S1).
+uint64_t mdtm_half_deviation(const uint32_t* x, uint32_t c);
+// The key of (H, S1); false when a half does not fit its field.
+bool mdtm_key(uint64_t H, uint64_t S1, uint64_t& key);
+
 // Per start rank, the 4 u64 of FastArgs::wstate: the colex rank of the
 // config's n - 3 largest positions (its group: the config with its three
 // lowest positions zeroed), then those positions as bytes in two words (n - 3

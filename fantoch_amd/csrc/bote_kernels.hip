@@ -93,15 +93,18 @@ __device__ __forceinline__ uint32_t sel(const uint32_t (&arr)[N], uint32_t i) {
 
 // --------------------------------------------------------- config result --
 // X: the extended key set (slots 10..19 and every leader's FPaxos moments,
-// al[f - 1][config-order leader], Input clients); PCTL: a top-K sweep with a
-// percentile objective (its own instantiations: the others keep their code
-// and registers)
-template <int N, bool X, bool PCTL = false>
+// al[f - 1][config-order leader], Input clients); PASSES (EVAL_*): a top-K
+// sweep with a percentile objective (EVAL_PCTL) or an MDTM objective
+// (EVAL_MDTM, which has the percentile passes too); these have their own
+// instantiations: the others keep their code and registers
+template <int N, bool X, int PASSES = EVAL_PLAIN>
 struct CfgOut {
   static constexpr int NS = X ? NSLOT_X : NSLOT;
+  static constexpr bool PCTL = PASSES >= EVAL_PCTL;
   Mom mom[NS];
   uint32_t mx[NS];  // Histogram::max per slot (top-K sweeps only: the MAX keys)
   uint32_t pt[PCTL ? MAXOBJ : 1];  // PCTL: twice Histogram::percentile per percentile objective
+  uint64_t mh[PASSES >= EVAL_MDTM ? MAXOBJ : 1];  // EVAL_MDTM: H (mdtm_key) per MDTM objective
   Mom al[X ? 2 : 1][X ? N : 1];
   uint32_t lead_orig;
   double score;
@@ -117,9 +120,10 @@ __device__ __forceinline__ bool slot_has(int s) {
 // ------------------------------------------------------------- eval one ---
 // Evaluate the configuration whose members are positions p[0..N) of the
 // server list (given order = config order).  `oi` is the output row (FULL).
-template <int N, bool FULL, bool X, bool PCTL = false>
+template <int N, bool FULL, bool X, int PASSES = EVAL_PLAIN>
 __device__ __forceinline__ void eval_config(const EvalArgs& a, const Smem& s, const uint32_t (&p)[N], bool sorted_in, uint64_t oi,
-                            CfgOut<N, X, PCTL>& out) {
+                            CfgOut<N, X, PASSES>& out) {
+  constexpr bool PCTL = PASSES >= EVAL_PCTL;
   using QC = QCfg<N>;
   using QT = QTab<N, X>;
   constexpr int NL = QT::NT;  // leaderless tables: compute_stats' q's, then the extended ones
@@ -433,11 +437,16 @@ __device__ __forceinline__ void eval_config(const EvalArgs& a, const Smem& s, co
   //     register list that the next objective reuses.  The values are
   //     regenerated as the passes above made them: leaderless from the nearest
   //     member and the lane's quorum table, FPaxos from the leader's column.
+  //     MDTM objectives (Histogram::mdtm, histogram.rs:221-235; EVAL_MDTM) take
+  //     the same pass with another accumulator: the slot's sum is known by
+  //     now, so the values above its mean are summed and counted against the
+  //     threshold T = floor(S1 / cnt) (bote_device.hpp mdtm_thr).
   if constexpr (PCTL) {
 #pragma unroll 1
     for (int o = 0; o < a.n_obj; ++o) {
       const uint32_t kind = a.obj_kind[o], sl = a.obj_slot[o];
-      if (kind < OBJ_PCTL) continue;
+      const bool mdtm = PASSES >= EVAL_MDTM && kind == OBJ_MDTM;
+      if (kind < OBJ_PCTL && !mdtm) continue;
       const uint32_t need = kind & PCTL_NEED_MASK;
       uint32_t L[PCTL_DEPTH];  // descending
 #pragma unroll
@@ -451,6 +460,30 @@ __device__ __forceinline__ void eval_config(const EvalArgs& a, const Smem& s, co
         }
       };
       const bool colocated = (sl >= 5 && sl < 10) || (sl >= 14 && sl < 18);
+      // MDTM: A = the sum of max(v - T, 0), B = the number of v > T; both fit
+      // 32 bits (v <= 2 * 16383, at most 4096 values)
+      MdtmThr mt{0, 0};
+      uint32_t mA = 0, mB = 0;
+      const uint32_t mcnt = colocated ? (uint32_t)N : nc;
+      if constexpr (PASSES >= EVAL_MDTM) {
+        if (mdtm) {
+          uint32_t s1 = 0;  // (`sl` is uniform: one scalar branch per slot)
+#pragma unroll
+          for (int q = 0; q < CfgOut<N, X, PASSES>::NS; ++q)
+            if ((uint32_t)q == sl) s1 = (uint32_t)out.mom[q].s1;
+          mt = mdtm_thr(s1, mcnt);
+        }
+      }
+      auto see = [&](uint32_t v) {
+        if constexpr (PASSES >= EVAL_MDTM) {
+          if (mdtm) {
+            mA += v > mt.T ? v - mt.T : 0u;
+            mB += v > mt.T ? 1u : 0u;
+            return;
+          }
+        }
+        put(v);
+      };
       // the slot's protocol: 0 af1, 1 ff1, 2 af2, 3 ff2, 4 e, then the
       // extended set's 5 tt1, 6 tt2, 7 tw1, 8 tw2, 9 fl1, 10 fl2
       const uint32_t b = sl < 10 ? sl % 5 : sl < 18 ? 5 + (sl - 10) % 4 : 9 + (sl - 18);
@@ -476,21 +509,30 @@ __device__ __forceinline__ void eval_config(const EvalArgs& a, const Smem& s, co
         };
         if (colocated) {
 #pragma unroll
-          for (int k = 0; k < N; ++k) put(value(cdk[k]));
+          for (int k = 0; k < N; ++k) see(value(cdk[k]));
         } else {
           for (uint32_t c = 0; c < nc; ++c) {
             const uint32_t off = s.clioff[c];
             uint32_t m = 0xFFFFFFFFu;
 #pragma unroll
             for (int k = 0; k < N; ++k) m = min(m, s.mat[off + mreg[k]] | (uint32_t)k);
-            put(value(m));
+            see(value(m));
           }
         }
       } else if (colocated) {
 #pragma unroll
-        for (int k = 0; k < N; ++k) put((s.mat[moff[k] + lr] >> LAT_SHIFT) + lq);
+        for (int k = 0; k < N; ++k) see((s.mat[moff[k] + lr] >> LAT_SHIFT) + lq);
       } else {
-        for (uint32_t c = 0; c < nc; ++c) put((s.mat[s.clioff[c] + lr] >> LAT_SHIFT) + lq);
+        for (uint32_t c = 0; c < nc; ++c) see((s.mat[s.clioff[c] + lr] >> LAT_SHIFT) + lq);
+      }
+      if constexpr (PASSES >= EVAL_MDTM) {
+        if (mdtm) {
+          const uint64_t h = mdtm_h(mcnt, mt, mA, mB);
+#pragma unroll
+          for (int q = 0; q < MAXOBJ; ++q)
+            if (q == o) out.mh[q] = h;
+          continue;
+        }
       }
       // the need-th largest, and the one above it (need <= the slot's count,
       // so neither is a list entry no value reached)
@@ -569,9 +611,10 @@ __device__ __forceinline__ void eval_config(const EvalArgs& a, const Smem& s, co
 }
 
 // ------------------------------------------------------------ the kernel --
-template <int N, bool FULL, bool X, bool PCTL = false>
+template <int N, bool FULL, bool X, int PASSES = EVAL_PLAIN>
 __global__ void __launch_bounds__(256) eval_kernel(EvalArgs a) {
-  static_assert(!(FULL && PCTL), "percentile objectives belong to top-K sweeps");
+  constexpr bool PCTL = PASSES >= EVAL_PCTL;
+  static_assert(!(FULL && PCTL), "percentile and MDTM objectives belong to top-K sweeps");
   constexpr int NLW = (QTab<N, X>::NT + 1) / 2;
   constexpr int NS = CfgOut<N, X>::NS;
   extern __shared__ __align__(16) unsigned char smem[];
@@ -647,9 +690,9 @@ __global__ void __launch_bounds__(256) eval_kernel(EvalArgs a) {
     }
     for (uint64_t t = 0; t < runlen; ++t) {
       const bool have = jobok && rank < rend;
-      CfgOut<N, X, PCTL> r;
+      CfgOut<N, X, PASSES> r;
       if (have) {
-        eval_config<N, FULL, X, PCTL>(a, s, p, sorted_in, rank - a.rb, r);
+        eval_config<N, FULL, X, PASSES>(a, s, p, sorted_in, rank - a.rb, r);
         if (r.valid) ++valid_cnt;
         if (a.want_digest) {
           uint32_t h = 0;
@@ -715,6 +758,8 @@ __global__ void __launch_bounds__(256) eval_kernel(EvalArgs a) {
                 if ((uint32_t)q == sl) {
                   if (PCTL && kind >= OBJ_PCTL)
                     key[o] = pctl_key(r.pt[o], r.mom[q].s1);
+                  else if (PASSES >= EVAL_MDTM && kind == OBJ_MDTM)
+                    key[o] = mdtm_key(r.mh[PASSES >= EVAL_MDTM ? o : 0], r.mom[q].s1);
                   else
                     key[o] = kind == OBJ_MEAN  ? r.mom[q].s1
                              : kind == OBJ_MAX ? max_key(r.mx[q], r.mom[q].s1)
@@ -850,13 +895,18 @@ size_t eval_smem_bytes(const EvalArgs& a, uint32_t n, uint32_t bd, bool topk) {
 
 // the kernel for config size n, full outputs or top-K, base or extended keys
 // (null: unsupported n), for the occupancy query and the launch alike
-// `pctl`: the top-K instantiation that also computes percentile objectives
-static const void* eval_fn(uint32_t n, bool full, bool keys, bool pctl) {
+// `passes` (EVAL_*): the top-K instantiation that also computes percentile
+// objectives, or those and MDTM objectives
+static const void* eval_fn(uint32_t n, bool full, bool keys, int passes) {
   switch (n) {
 #define FN_CASE(NN)                                                                                             \
   case NN:                                                                                                      \
-    if (pctl && !full)                                                                                          \
-      return keys ? (const void*)eval_kernel<NN, false, true, true> : (const void*)eval_kernel<NN, false, false, true>; \
+    if (passes >= EVAL_MDTM && !full)                                                                           \
+      return keys ? (const void*)eval_kernel<NN, false, true, EVAL_MDTM>                                        \
+                  : (const void*)eval_kernel<NN, false, false, EVAL_MDTM>;                                      \
+    if (passes == EVAL_PCTL && !full)                                                                           \
+      return keys ? (const void*)eval_kernel<NN, false, true, EVAL_PCTL>                                        \
+                  : (const void*)eval_kernel<NN, false, false, EVAL_PCTL>;                                      \
     return keys ? (full ? (const void*)eval_kernel<NN, true, true> : (const void*)eval_kernel<NN, false, true>) \
                 : (full ? (const void*)eval_kernel<NN, true, false> : (const void*)eval_kernel<NN, false, false>);
     FN_CASE(2) FN_CASE(3) FN_CASE(4) FN_CASE(5) FN_CASE(6) FN_CASE(7) FN_CASE(8) FN_CASE(9)
@@ -866,16 +916,15 @@ static const void* eval_fn(uint32_t n, bool full, bool keys, bool pctl) {
   }
 }
 
-int eval_occupancy(uint32_t n, bool full, uint32_t bd, size_t shm, bool keys, bool pctl) {
-  const void* k = eval_fn(n, full, keys, pctl);
+int eval_occupancy(uint32_t n, bool full, uint32_t bd, size_t shm, bool keys, int passes) {
+  const void* k = eval_fn(n, full, keys, passes);
   return k ? kernel_occupancy(k, bd, shm, 1) : 0;
 }
 
 hipError_t launch_eval(const EvalArgs& a, uint32_t n, bool full, uint32_t grid, uint32_t bd, size_t shm,
                        hipStream_t st) {
-  bool pctl = false;  // a percentile objective among a top-K sweep's (bote_kernels.hpp OBJ_PCTL)
-  for (int o = 0; o < a.n_obj && !full; ++o) pctl = pctl || a.obj_kind[o] >= OBJ_PCTL;
-  const void* k = eval_fn(n, full, a.keys != 0, pctl);
+  // a percentile or MDTM objective among a top-K sweep's (bote_kernels.hpp EVAL_*)
+  const void* k = eval_fn(n, full, a.keys != 0, full ? (int)EVAL_PLAIN : eval_passes(a.obj_kind, a.n_obj));
   return k ? launch_kernel(k, a, grid, bd, shm, st) : hipErrorInvalidValue;
 }
 

@@ -8,7 +8,9 @@ namespace bote {
 constexpr int NSLOT = 10;
 constexpr int G_MERGE_LISTS = 8;  // lists merged per workgroup
 enum { SLOT_AF1 = 0, SLOT_FF1 = 1, SLOT_AF2 = 2, SLOT_FF2 = 3, SLOT_E = 4 };
-enum { OBJ_SCORE = 0, OBJ_MEAN = 1, OBJ_COV = 2, OBJ_MAX = 16 };
+// (OBJ_MDTM lies between OBJ_MAX and OBJ_PCTL: tests on a kind are equalities,
+// except `>= OBJ_PCTL`, the percentiles)
+enum { OBJ_SCORE = 0, OBJ_MEAN = 1, OBJ_COV = 2, OBJ_MAX = 16, OBJ_MDTM = 18 };
 // A percentile objective (BOTE_OBJ_PCTL) as the kernels see it in obj_kind:
 // the host (bote_capi_sweep.hip, pctl_device_kind) turns bp and the slot's
 // count into OBJ_PCTL | (whole ? PCTL_WHOLE : 0) | need, need = 1..PCTL_DEPTH:
@@ -221,8 +223,11 @@ struct FastArgs {
 // percentile objective; FAST_MAX also carries every slot's maximum (the worst
 // client) for BOTE_OBJ_MAX objectives; FAST_LIST carries every slot's
 // PCTL_FAST_DEPTH largest values, descending, for percentile objectives of
-// need <= PCTL_FAST_DEPTH (entry 0 serves the MAX objectives of such a sweep)
-enum { FAST_PLAIN = 0, FAST_MAX = 1, FAST_LIST = 2 };
+// need <= PCTL_FAST_DEPTH (entry 0 serves the MAX objectives of such a sweep);
+// FAST_MDTM treats BOTE_OBJ_MDTM objectives (a second pass over the clients
+// against each slot's mean) and carries no maxima or lists: a sweep with an
+// MDTM objective beside a MAX or percentile one runs the generic kernel
+enum { FAST_PLAIN = 0, FAST_MAX = 1, FAST_LIST = 2, FAST_MDTM = 3 };
 size_t fast_smem_bytes(const FastArgs& a, uint32_t n, int tail);
 int fast_occupancy(uint32_t n, int tail, size_t shm);
 // (e0, e1: events carried by the dispatch itself, bote_launch.hpp, for a timed launch)
@@ -249,8 +254,19 @@ hipError_t launch_group(const FastArgs& a, uint32_t n, bool def_objectives, uint
 
 // ---- generic exact kernel (bote_kernels.hip)
 size_t eval_smem_bytes(const EvalArgs& a, uint32_t n, uint32_t bd, bool topk);
-// (pctl: the top-K instantiation launch_eval takes for a sweep with a percentile objective)
-int eval_occupancy(uint32_t n, bool full, uint32_t bd, size_t shm, bool keys = false, bool pctl = false);
+// The generic kernel's top-K instantiations by the passes a sweep's objectives
+// add to a config (each level has the ones below it): EVAL_PCTL one pass per
+// percentile objective, EVAL_MDTM also one per MDTM objective.  Sweeps with
+// neither, and full outputs, take EVAL_PLAIN and keep their code and registers.
+enum { EVAL_PLAIN = 0, EVAL_PCTL = 1, EVAL_MDTM = 2 };
+inline int eval_passes(const uint32_t* obj_kind, int n_obj) {
+  int e = EVAL_PLAIN;
+  for (int o = 0; o < n_obj; ++o)
+    e = obj_kind[o] == OBJ_MDTM ? (int)EVAL_MDTM : obj_kind[o] >= OBJ_PCTL && e < EVAL_PCTL ? (int)EVAL_PCTL : e;
+  return e;
+}
+// (passes: the top-K instantiation launch_eval takes for the sweep's objectives, eval_passes)
+int eval_occupancy(uint32_t n, bool full, uint32_t bd, size_t shm, bool keys = false, int passes = EVAL_PLAIN);
 hipError_t launch_eval(const EvalArgs& a, uint32_t n, bool full, uint32_t grid, uint32_t bd, size_t shm,
                        hipStream_t st);
 

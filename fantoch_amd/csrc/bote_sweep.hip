@@ -43,6 +43,7 @@ struct FastSmem {
   uint64_t* binom;
   uint32_t* cmax;  // FAST_MAX: per position, the largest client latency of its column
   uint2* c4;       // FAST_LIST: per position, its column's four largest client latencies, descending (4 x u16)
+  uint64_t* ch;    // FAST_MDTM: per position, H of its client column (mdtm_key; shift invariant, so also H of ff1 and ff2)
   TopkLds tk;
 };
 
@@ -65,11 +66,12 @@ __host__ __device__ inline size_t fast_layout(const FastArgs& a, int N, int NLW,
   off[12] = o; o += 48;                       // cnt[1 + MAXOBJ]
   off[13] = o; o += tail == FAST_MAX ? (size_t)a.ns * 4 : 0;   // cmax
   off[14] = o; o += tail == FAST_LIST ? (size_t)a.ns * 8 : 0;  // c4 (8-byte aligned: every region above is)
+  off[15] = o; o += tail == FAST_MDTM ? (size_t)a.ns * 8 : 0;  // ch (the same)
   return o;
 }
 
 size_t fast_smem_bytes(const FastArgs& a, uint32_t n, int tail) {
-  size_t off[15];
+  size_t off[16];
   int nl = 0;
   switch (n) {
 #define NL_CASE(NN) case NN: nl = QCfg<NN>::NL; break;
@@ -140,11 +142,23 @@ __device__ __forceinline__ uint32_t list_at(const uint32_t (&l)[2], uint32_t k) 
 // (v_pk_max_u16 / v_pk_min_u16).  After the loop the two streams' lists are
 // merged.  A dead client enters as 0 and cannot displace a live value among
 // the largest `need <= nc`.  No LDS traffic is added here either.
+// TAIL == FAST_MDTM: H of the tables in the mask `mdm` (bit t: table t has an
+// MDTM objective; uniform over the launch) into MH.  A table's mean is known
+// only after the loop, so the quads are passed over a second time: the same
+// loads, packed nearest-member min, qtab reads and remainder mask, then per
+// table in the mask a packed saturating subtract of T = floor(S1 / nc)
+// (v_pk_sub_u16 clamp), whose sum (v_dot2_u32_u16) is A = the sum of max(x - T,
+// 0) and whose non-zero halves (v_pk_min_u16 with 1, v_dot2_u32_u16) count B =
+// the number of x > T; H = nc A - r B (bote_device.hpp mdtm_h).  A dead
+// remainder client is masked to 0 before the subtract and adds nothing to
+// either.  x <= 2 * 4095 and nc <= 4096, so A <= 2^25 and B <= 2^12 stay in 32
+// bits for the whole loop.  Tables outside the mask, and a launch with an
+// empty mask, pay nothing.
 template <int N, int NL, int TAIL>
 __device__ __forceinline__ void client_quads(const unsigned char* B, uint32_t cqt, uint32_t nq, uint32_t rem,
                                              uint32_t flushQ, const uint32_t (&colT)[N], uint32_t qlane,
                                              uint32_t (&S1)[NL], uint64_t (&S2)[NL], uint32_t (&MX)[NL],
-                                             uint32_t (&ML)[NL][2]) {
+                                             uint32_t (&ML)[NL][2], uint32_t mdm, uint32_t nc, uint64_t (&MH)[NL]) {
   const us2 ones = {1, 1};
   constexpr int NQ = NL == 3 ? 8 : 4;  // qtab words per quad
   uint32_t s2[NL];
@@ -182,15 +196,17 @@ __device__ __forceinline__ void client_quads(const unsigned char* B, uint32_t cq
     }
   };
   // stage 3a: the nearest members' quorum latencies (qtab sits at LDS offset
-  // 0, so qlane < 2^QSH and the member plane offset can be OR-ed in)
-  auto qread = [&](us2 lo, us2 hi, uint32_t (&q)[NQ]) {
+  // 0, so qlane < 2^QSH and the member plane offset can be OR-ed in);
+  // `plane2`: the third table's plane too (the second pass of FAST_MDTM skips it
+  // when that table has no MDTM objective)
+  auto qread = [&](us2 lo, us2 hi, uint32_t (&q)[NQ], bool plane2 = true) {
     constexpr uint32_t QM = 15u << QSH;
     const uint32_t L = as_u32(lo), H = as_u32(hi);
     q[0] = ld32(B, ((L << QSH) & QM) | qlane);
     q[1] = ld32(B, ((L >> (16 - QSH)) & QM) | qlane);
     q[2] = ld32(B, ((H << QSH) & QM) | qlane);
     q[3] = ld32(B, ((H >> (16 - QSH)) & QM) | qlane);
-    if (NL == 3) {
+    if (NL == 3 && plane2) {
       const uint32_t P2 = (uint32_t)N << QSH;  // second plane follows the first
       q[NQ - 4] = ld32(B, qlane + P2 + ((L & 15u) << QSH));
       q[NQ - 3] = ld32(B, qlane + P2 + (((L >> 16) & 15u) << QSH));
@@ -307,6 +323,65 @@ __device__ __forceinline__ void client_quads(const unsigned char* B, uint32_t cq
       ML[t][1] = c[2] | (c[3] << 16);
     }
   }
+  if constexpr (TAIL == FAST_MDTM) {
+#pragma unroll
+    for (int t = 0; t < NL; ++t) MH[t] = 0;
+    if (mdm) {
+      MdtmThr thr[NL];
+      us2 pT[NL];  // T in both halves (T <= 2 * 4095)
+      uint32_t A[NL], C[NL];
+#pragma unroll
+      for (int t = 0; t < NL; ++t) {
+        thr[t] = (mdm >> t) & 1u ? mdtm_thr(S1[t], nc) : MdtmThr{0, 0};  // (uniform: no division for the others)
+        pT[t] = us2{(unsigned short)thr[t].T, (unsigned short)thr[t].T};
+        A[t] = C[t] = 0;
+      }
+      auto above1 = [&](int t, us2 dlo, us2 dhi, uint32_t ql01, uint32_t ql23, uint32_t mlo, uint32_t mhi) {
+        if (!(mdm & (1u << t))) return;  // uniform
+        const us2 a01 = as_us2(as_u32(dlo + as_us2(ql01)) & mlo), a23 = as_us2(as_u32(dhi + as_us2(ql23)) & mhi);
+        const us2 e01 = __builtin_elementwise_sub_sat(a01, pT[t]), e23 = __builtin_elementwise_sub_sat(a23, pT[t]);
+        A[t] = __builtin_amdgcn_udot2(e01, ones, A[t], false);
+        A[t] = __builtin_amdgcn_udot2(e23, ones, A[t], false);
+        C[t] = __builtin_amdgcn_udot2(__builtin_elementwise_min(e01, ones), ones, C[t], false);
+        C[t] = __builtin_amdgcn_udot2(__builtin_elementwise_min(e23, ones), ones, C[t], false);
+      };
+      auto quad2 = [&](uint32_t g8, uint32_t mlo, uint32_t mhi) {
+        uint2 w[N];
+        uint32_t q[NQ] = {};
+        us2 lo, hi;
+        load(g8, w);
+        nearest(w, lo, hi);
+        qread(lo, hi, q, (mdm >> 2) & 1u);  // (uniform)
+        const us2 dlo = lo >> (us2)4, dhi = hi >> (us2)4;
+        above1(0, dlo, dhi, __builtin_amdgcn_perm(q[1], q[0], 0x05040100u),
+               __builtin_amdgcn_perm(q[3], q[2], 0x05040100u), mlo, mhi);
+        if (NL >= 2)
+          above1(NL >= 2 ? 1 : 0, dlo, dhi, __builtin_amdgcn_perm(q[1], q[0], 0x07060302u),
+                 __builtin_amdgcn_perm(q[3], q[2], 0x07060302u), mlo, mhi);
+        if (NL == 3)
+          above1(NL - 1, dlo, dhi, __builtin_amdgcn_perm(q[NQ - 3], q[NQ - 4], 0x05040100u),
+                 __builtin_amdgcn_perm(q[NQ - 1], q[NQ - 2], 0x05040100u), mlo, mhi);
+      };
+      for (uint32_t g2 = 0; g2 < nq; ++g2) quad2(g2 * 8, ~0u, ~0u);
+      if (rem) quad2(nq * 8, rem >= 2 ? ~0u : 0x0000FFFFu, rem == 3 ? 0x0000FFFFu : 0u);
+#pragma unroll
+      for (int t = 0; t < NL; ++t) MH[t] = mdtm_h(nc, thr[t], A[t], C[t]);
+    }
+  }
+}
+
+// FAST_MDTM: H (mdtm_key) of n values x[0..n) with sum s1, a two-step
+// computation in registers (the colocated slots: n <= 16 members)
+template <int N>
+__device__ __forceinline__ uint64_t small_mdtm_h(const uint32_t (&x)[N], uint32_t s1) {
+  const MdtmThr t = mdtm_thr(s1, (uint32_t)N);
+  uint32_t A = 0, C = 0;
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+    A += x[k] > t.T ? x[k] - t.T : 0u;
+    C += x[k] > t.T ? 1u : 0u;
+  }
+  return mdtm_h((uint32_t)N, t, A, C);
 }
 
 // ---------------------------------------------------------- the kernel ----
@@ -329,6 +404,16 @@ __device__ __forceinline__ void client_quads(const unsigned char* B, uint32_t cq
 // across it), colocated FPaxos from the N-step loop.  Entry 0 is the maximum,
 // so the MAX objectives of such a sweep are served from the lists.  Keys are
 // built and withdrawn as for FAST_MAX.
+// TAIL == FAST_MDTM: the variant for sweeps with an MDTM objective and no MAX
+// or percentile one (base key set).  Only the slots that have an MDTM
+// objective are treated (a mask over the launch, from obj_kind / obj_slot):
+// the Input leaderless tables by client_quads' second pass; Input FPaxos from
+// H of the leader's client column (staged per position, ch: H is shift
+// invariant, the quorum latency drops out); the colocated leaderless slots
+// from the lane's quorum table read back, colocated FPaxos from the N-step
+// loop's values again, both in registers (small_mdtm_h).  Each H goes into its
+// objectives' keys at once, before finish_config, which leaves them alone;
+// they are withdrawn when it defers the config.
 template <int N, int TAIL>
 __global__ void __launch_bounds__(FAST_BD, 4) sweep_fast_kernel(FastArgs a) {
   using QC = QCfg<N>;
@@ -336,7 +421,7 @@ __global__ void __launch_bounds__(FAST_BD, 4) sweep_fast_kernel(FastArgs a) {
   constexpr int NLW = NL <= 2 ? 1 : 2;
   constexpr int P = Pow2<N - 1>::v;  // off-diagonal row values, padded
   extern __shared__ __align__(16) unsigned char smem[];
-  size_t off[15];
+  size_t off[16];
   fast_layout(a, N, NLW, TAIL, off);
   FastSmem s;
   s.base = smem;
@@ -350,6 +435,7 @@ __global__ void __launch_bounds__(FAST_BD, 4) sweep_fast_kernel(FastArgs a) {
   s.binom = (uint64_t*)(smem + off[7]);
   s.cmax = (uint32_t*)(smem + off[13]);
   s.c4 = (uint2*)(smem + off[14]);
+  s.ch = (uint64_t*)(smem + off[15]);
   s.tk.top = (Rec*)(smem + off[8]);
   s.tk.cand = (Rec*)(smem + off[9]);
   s.tk.tmp = (Rec*)(smem + off[10]);
@@ -393,6 +479,16 @@ __global__ void __launch_bounds__(FAST_BD, 4) sweep_fast_kernel(FastArgs a) {
       for (uint32_t c = 0; c < a.nc; ++c) list_insert(cl, ld16(B, col + (c >> 2) * 8 + (c & 3) * 2) >> LAT_SHIFT);
       s.c4[i] = make_uint2(cl[0] | (cl[1] << 16), cl[2] | (cl[3] << 16));
     }
+    if constexpr (TAIL == FAST_MDTM) {  // (a pass of its own: once per block)
+      const MdtmThr t = mdtm_thr((uint32_t)c1, a.nc);
+      uint32_t A = 0, C = 0;
+      for (uint32_t c = 0; c < a.nc; ++c) {
+        const uint32_t v = ld16(B, col + (c >> 2) * 8 + (c & 3) * 2) >> LAT_SHIFT;
+        A += v > t.T ? v - t.T : 0u;
+        C += v > t.T ? 1u : 0u;
+      }
+      s.ch[i] = mdtm_h(a.nc, t, A, C);
+    }
     s.cs1[i] = (uint32_t)c1;
     s.cs2[i] = c2;
     s.vcol[i] = (double)((uint64_t)a.nc * c2 - c1 * c1);  // exact: < 2^53
@@ -408,6 +504,15 @@ __global__ void __launch_bounds__(FAST_BD, 4) sweep_fast_kernel(FastArgs a) {
   const uint64_t outer = (njobs + G - 1) / G;
   const double pnc1 = a.p_fmean * (double)nc, pnc2 = a.p_emean * (double)nc;
   uint64_t valid_cnt = 0, digest = 0;
+  // FAST_MDTM: the slots (bit = slot) and the leaderless tables (bit = table)
+  // that have an MDTM objective
+  uint32_t mds = 0, mdm = 0;
+  if constexpr (TAIL == FAST_MDTM) {
+    for (int o = 0; o < a.n_obj; ++o)
+      if (a.obj_kind[o] == OBJ_MDTM) mds |= 1u << a.obj_slot[o];
+    mdm = ((mds >> SLOT_AF1) & 1u) << QC::idx_a1 | ((mds >> SLOT_AF2) & 1u) << QC::idx_a2 |
+          ((mds >> SLOT_E) & 1u) << QC::idx_e;
+  }
 
   for (uint64_t it = 0; it < outer; ++it) {
     const uint64_t job = it * G + (uint64_t)blockIdx.x * FAST_BD + tid;
@@ -513,14 +618,26 @@ __global__ void __launch_bounds__(FAST_BD, 4) sweep_fast_kernel(FastArgs a) {
           Mom mom[NSLOT];
           uint32_t mx[NSLOT];     // FAST_MAX: the slots' maxima
           uint32_t l4[NSLOT][2];  // FAST_LIST: the slots' four largest values, packed (FPaxos: less the quorum latency)
+          // FAST_MDTM: slot q's H into the keys of its MDTM objectives (`q` is
+          // a constant and the objectives uniform: scalar branches)
+          auto mdtm_keys = [&](int q, uint64_t h) {
+#pragma unroll
+            for (int o = 0; o < MAXOBJ; ++o) {
+              if (o >= a.n_obj) break;
+              if (a.obj_kind[o] != OBJ_MDTM || a.obj_slot[o] != (uint32_t)q) continue;
+              ok[o] = true;
+              key[o] = mdtm_key(h, mom[q].s1);
+            }
+          };
           // Input leaderless: the hot loop (first, so little is live across it)
           {
             uint32_t S1[NL];
             uint64_t S2[NL];
             uint32_t MX[NL];
             uint32_t ML[NL][2];
+            uint64_t MH[NL];
             client_quads<N, NL, TAIL>(B, s.cqt, ABLATE(a, 1) ? 0u : nq, ABLATE(a, 1) ? 0u : rem, a.s2_flush, colT,
-                                      qlane, S1, S2, MX, ML);
+                                      qlane, S1, S2, MX, ML, mdm, nc, MH);
             if (ABLATE(a, 1)) {  // timing only: non-degenerate dummy sums (nothing defers)
 #pragma unroll
               for (int t = 0; t < NL; ++t) {
@@ -544,6 +661,11 @@ __global__ void __launch_bounds__(FAST_BD, 4) sweep_fast_kernel(FastArgs a) {
                 l4[SLOT_E][h] = ML[QC::idx_e][h];
               }
             }
+            if constexpr (TAIL == FAST_MDTM) {
+              if ((mds >> SLOT_AF1) & 1u) mdtm_keys(SLOT_AF1, MH[QC::idx_a1]);
+              if ((mds >> SLOT_AF2) & 1u) mdtm_keys(SLOT_AF2, MH[QC::idx_a2]);
+              if ((mds >> SLOT_E) & 1u) mdtm_keys(SLOT_E, MH[QC::idx_e]);
+            }
           }
           // Input FPaxos: moments from the leader column's sums
           mom[SLOT_FF1] = leader_mom(s.cs1[lp], s.cs2[lp], nc, lq2);
@@ -557,6 +679,10 @@ __global__ void __launch_bounds__(FAST_BD, 4) sweep_fast_kernel(FastArgs a) {
             const uint2 c = s.c4[lp];
             l4[SLOT_FF1][0] = l4[SLOT_FF2][0] = c.x;
             l4[SLOT_FF1][1] = l4[SLOT_FF2][1] = c.y;
+          }
+          if constexpr (TAIL == FAST_MDTM) {
+            if ((mds >> SLOT_FF1) & 1u) mdtm_keys(SLOT_FF1, s.ch[lp]);
+            if ((mds >> SLOT_FF2) & 1u) mdtm_keys(SLOT_FF2, s.ch[lp]);
           }
           // Colocated: leaderless values are the members' own quorum latencies;
           // FPaxos reads the leader's column of the config submatrix.
@@ -611,6 +737,37 @@ __global__ void __launch_bounds__(FAST_BD, 4) sweep_fast_kernel(FastArgs a) {
                 l4[5 + SLOT_AF1][h] = cl[QC::idx_a1][h];
                 l4[5 + SLOT_AF2][h] = cl[QC::idx_a2][h];
                 l4[5 + SLOT_E][h] = cl[QC::idx_e][h];
+              }
+            }
+            if constexpr (TAIL == FAST_MDTM) {
+              if (((mds >> (5 + SLOT_FF1)) | (mds >> (5 + SLOT_FF2))) & 1u) {
+                // the members' latencies to the leader (the N-step loop's values
+                // again; the quorum latency drops out of H)
+                uint32_t x[N];
+#pragma unroll
+                for (int k = 0; k < N; ++k) x[k] = ld16(B, lcol + rowq[k]) >> LAT_SHIFT;
+                const uint64_t h = small_mdtm_h<N>(x, f1 - (uint32_t)N * lq2);
+                if ((mds >> (5 + SLOT_FF1)) & 1u) mdtm_keys(5 + SLOT_FF1, h);
+                if ((mds >> (5 + SLOT_FF2)) & 1u) mdtm_keys(5 + SLOT_FF2, h);
+              }
+              // the members' own quorum latencies, read back from the lane's
+              // qtab planes: word j holds tables 0 and 1, word N + j table 2
+#pragma unroll
+              for (int t = 0; t < NL; ++t) {
+                const uint32_t want = ((mds >> (5 + SLOT_AF1)) & 1u) << QC::idx_a1 |
+                                      ((mds >> (5 + SLOT_AF2)) & 1u) << QC::idx_a2 |
+                                      ((mds >> (5 + SLOT_E)) & 1u) << QC::idx_e;
+                if (!((want >> t) & 1u)) continue;
+                uint32_t x[N];
+#pragma unroll
+                for (int j = 0; j < N; ++j) {
+                  const uint32_t w = ld32(B, qlane + ((uint32_t)(t == 2 ? N + j : j) << QSH));
+                  x[j] = t == 1 ? w >> 16 : w & 0xFFFFu;
+                }
+                const uint64_t h = small_mdtm_h<N>(x, cS1[t]);
+                if (QC::idx_a1 == t && ((mds >> (5 + SLOT_AF1)) & 1u)) mdtm_keys(5 + SLOT_AF1, h);
+                if (QC::idx_a2 == t && ((mds >> (5 + SLOT_AF2)) & 1u)) mdtm_keys(5 + SLOT_AF2, h);
+                if (QC::idx_e == t && ((mds >> (5 + SLOT_E)) & 1u)) mdtm_keys(5 + SLOT_E, h);
               }
             }
           }
@@ -683,8 +840,9 @@ static const void* fast_fn(uint32_t n, int tail) {
   switch (n) {
 #define FN_CASE(NN)                                                                  \
   case NN:                                                                           \
-    return tail == FAST_LIST  ? (const void*)sweep_fast_kernel<NN, FAST_LIST>        \
-           : tail == FAST_MAX ? (const void*)sweep_fast_kernel<NN, FAST_MAX>         \
+    return tail == FAST_MDTM   ? (const void*)sweep_fast_kernel<NN, FAST_MDTM>       \
+           : tail == FAST_LIST ? (const void*)sweep_fast_kernel<NN, FAST_LIST>       \
+           : tail == FAST_MAX  ? (const void*)sweep_fast_kernel<NN, FAST_MAX>        \
                               : (const void*)sweep_fast_kernel<NN, FAST_PLAIN>;
     FN_CASE(2) FN_CASE(3) FN_CASE(4) FN_CASE(5) FN_CASE(6) FN_CASE(7) FN_CASE(8) FN_CASE(9)
     FN_CASE(10) FN_CASE(11) FN_CASE(12) FN_CASE(13) FN_CASE(14) FN_CASE(15) FN_CASE(16)

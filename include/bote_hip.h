@@ -101,6 +101,18 @@ extern "C" {
  * percentile that needs more than 8 of the slot's largest values
  * (bote_percentile_index) is BOTE_E_RANGE. */
 #define BOTE_OBJ_PCTL(bp) (0x10000u | (bp))
+/* min Histogram::mdtm of `slot` (histogram.rs:221-235: the mean distance to the
+ * mean, Stats::MDTM), then min mean.  For the slot's c values x_i with exact
+ * sum S1:
+ *   H   = sum over { i : c x_i > S1 } of (c x_i - S1)     (sum |c x_i - S1| = 2 H)
+ *   key = (H << 27) | S1
+ * Histogram::mdtm is 2 H / c^2 and c is the same for every config of a sweep,
+ * so the order by H is the order by the exact MDTM (the reference's f64 value
+ * differs from it by rounding only; near-ties are ordered exactly, as MEAN's
+ * are).  S1 <= 4096 * 2 * 16383 < 2^27 - 1 and H <= c^2 * 32766 / 4 < 2^37.
+ * Kind 17 and kinds 19.. are not defined. */
+#define BOTE_OBJ_MDTM 18
+#define BOTE_MDTM_SUM_BITS 27
 
 /* Sweep kernel paths (bote_sweep_create_ex); every path is exact. */
 #define BOTE_KERNEL_AUTO 0    /* group kernel when eligible, else fast, else generic */
@@ -287,7 +299,14 @@ int bote_sweep_create(const bote_planet* p, const uint32_t* servers, uint32_t ns
  * its slot: up to 4 run on the fast kernel's sorted-list variant (AUTO or
  * forced fast, base key set, eligible planet), 5..8 on the generic kernel
  * (a forced fast kernel is BOTE_E_ARG), as do the extended key set and
- * ineligible planets; a forced group kernel is BOTE_E_ARG as for MAX. */
+ * ineligible planets; a forced group kernel is BOTE_E_ARG as for MAX.
+ * A BOTE_OBJ_MDTM objective runs on the fast kernel's MDTM variant, which
+ * passes over the clients a second time once a slot's sum is known (AUTO or
+ * forced fast, base key set, eligible planet, no MAX or percentile objective
+ * in the same sweep), else on the generic kernel; that variant carries no
+ * maxima or lists, so a forced fast kernel with a MAX or percentile objective
+ * beside an MDTM one is BOTE_E_ARG, and a forced group kernel is BOTE_E_ARG
+ * as for MAX. */
 int bote_sweep_create_ex(const bote_planet* p, const uint32_t* servers, uint32_t ns,
                          const uint32_t* clients, uint32_t nc, uint32_t n,
                          const bote_objective* objs, uint32_t n_obj, uint32_t K,

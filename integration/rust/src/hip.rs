@@ -39,6 +39,9 @@ pub const BOTE_OBJ_MAX: u32 = 16;
 pub const fn bote_obj_pctl(bp: u32) -> u32 {
     0x10000 | bp
 }
+/// min Histogram::mdtm of a slot (Stats::MDTM), then min sum: key = (H << 27) | sum with
+/// H = the sum over the slot's values above its mean of (count * x - sum); mdtm = 2 H / count^2
+pub const BOTE_OBJ_MDTM: u32 = 18;
 
 #[repr(C)]
 pub struct bote_planet {
