@@ -64,6 +64,7 @@ EXPORTS = [
     "bote_sweep_timing", "bote_sweep_grid", "bote_sweep_is_fast", "bote_sweep_split", "bote_sweep_create_ex", "bote_search_topk", "bote_sweep_deferred", "bote_eval_leaderless", "bote_evolving_chains",
     "bote_search_create", "bote_search_launch", "bote_search_result", "bote_search_bounds", "bote_search_destroy",
     "bote_eval_keys", "bote_sweep_create_keys", "bote_percentile_index",
+    "bote_sweep_create_pinned", "bote_pinned_total", "bote_pinned_config",
 ]
 KERNELS = {None: 0, "auto": 0, "generic": 1, "fast": 2, "group": 3}
 
@@ -178,6 +179,14 @@ def lib():
     L.bote_colex_unrank.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, _u32p]
     L.bote_binomial.restype = C.c_uint64
     L.bote_binomial.argtypes = [C.c_uint32, C.c_uint32]
+    if hasattr(L, "bote_sweep_create_pinned"):  # (the same)
+        L.bote_sweep_create_pinned.argtypes = [_vp, _u32p, C.c_uint32, _u32p, C.c_uint32, C.c_uint32, _u32p, C.c_uint32,
+                                               C.POINTER(Objective), C.c_uint32, C.c_uint32,
+                                               C.POINTER(RankingParamsC), C.c_int, C.c_int, C.POINTER(_vp)]
+        L.bote_pinned_total.restype = C.c_uint64
+        L.bote_pinned_total.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]
+        L.bote_pinned_config.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, _u32p, C.c_uint32, _u32p,
+                                         C.POINTER(C.c_uint64)]
     if hasattr(L, "bote_percentile_index"):  # (absent from an older BOTE_LIB_PATH build loaded for A/B timing)
         L.bote_percentile_index.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_int)]
     _LIB = L
@@ -226,3 +235,17 @@ def colex_unrank(rank: int, n: int, ns: int) -> np.ndarray:
     out = np.zeros(n, np.uint32)
     check(lib().bote_colex_unrank(rank, n, ns, out))
     return out
+
+
+def pinned_total(ns: int, n: int, n_pinned: int) -> int:
+    """C(ns - n_pinned, n - n_pinned): the rank space of a pinned sweep (0 on overflow or bad sizes)."""
+    return int(lib().bote_pinned_total(ns, n, n_pinned))
+
+
+def pinned_config(pinned_rank: int, n: int, ns: int, pinned):
+    """(positions, full colex rank) of pinned rank `pinned_rank` among the n-supersets of `pinned`
+    (positions into the server list): the config's n ascending positions."""
+    pin = u32(pinned)
+    out, rank = np.zeros(n, np.uint32), C.c_uint64(0)
+    check(lib().bote_pinned_config(pinned_rank, n, ns, pin, len(pin), out, C.byref(rank)))
+    return out, rank.value

@@ -741,17 +741,32 @@ class Sweep:
 
     def __init__(self, dp: DevicePlanet, servers: Sequence[int], clients: Sequence[int], n: int,
                  objectives=DEFAULT_OBJECTIVES, K: int = 100, ranking: Optional[RankingParams] = DEFAULT_RANKING,
-                 digest: bool = False, kernel: Optional[str] = None, keys: int = _lib.KEYS_BASE):
+                 digest: bool = False, kernel: Optional[str] = None, keys: int = _lib.KEYS_BASE,
+                 pinned: Optional[Sequence[int]] = None):
         """kernel: None/'auto' (the library's choice), or force 'generic', 'fast'
         or 'group' (every path is exact; bote_sweep_create_keys).  keys: the
-        key set (_lib.KEYS_BASE, or KEYS_TEMPO_ALL_LEADERS for BASELINE config 5)."""
+        key set (_lib.KEYS_BASE, or KEYS_TEMPO_ALL_LEADERS for BASELINE config 5).
+        pinned: positions into `servers` that every swept config contains
+        (bote_sweep_create_pinned, base key set): `total`, `launch` and `split`
+        then count pinned ranks, and records still carry full colex ranks."""
         self.dp, self.n, self.K, self.keys = dp, n, K, keys
+        self.pinned = None if pinned is None else u32(pinned)
         self.servers, self.clients = u32(servers), u32(clients)
         self.objectives = list(objectives)
         self.ranking, self.digest = ranking, bool(digest)
         objs = (_lib.Objective * max(len(self.objectives), 1))(*[_lib.Objective(k, s) for k, s in self.objectives])
         rp = C.byref(_lib.ranking_params_c(ranking)) if ranking is not None else None
         h = C.c_void_p()
+        if self.pinned is not None:
+            if keys != _lib.KEYS_BASE:
+                raise ValueError("a pinned sweep computes the base key set")
+            check(lib().bote_sweep_create_pinned(dp.h, self.servers, len(self.servers), self.clients,
+                                                 len(self.clients), n, self.pinned, len(self.pinned), objs,
+                                                 len(self.objectives), K, rp, 1 if digest else 0,
+                                                 _lib.KERNELS[kernel], C.byref(h)))
+            self.h = h
+            self.total = _lib.pinned_total(len(self.servers), n, len(self.pinned))
+            return
         check(lib().bote_sweep_create_keys(dp.h, self.servers, len(self.servers), self.clients, len(self.clients), n,
                                            objs, len(self.objectives), K, rp, 1 if digest else 0,
                                            _lib.KERNELS[kernel], keys, C.byref(h)))
@@ -791,6 +806,8 @@ class Sweep:
                                 self.servers.astype(np.uint64), self.clients.astype(np.uint64),
                                 np.asarray(self.objectives, np.uint64).reshape(-1),
                                 np.asarray(self.dp.planet.lat, np.uint64).reshape(-1)])
+        if self.pinned is not None:  # (a checkpoint of another pinned set, or of the unpinned sweep, is refused)
+            ident = np.concatenate([ident, np.array([len(self.pinned)], np.uint64), self.pinned.astype(np.uint64)])
         dev = torch.device("cuda", self.dp.device)
         st = torch.cuda.current_stream(dev).cuda_stream
         nb = self.result_bytes()

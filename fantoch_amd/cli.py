@@ -20,6 +20,7 @@ main.rs:31-60).  Subcommands expose them, and the sweep the hot path serves:
   python -m fantoch_amd sweep (--synthetic R [--seed S] | --lat-dir D) --n N [--K 100]
                         [--objectives default|config5|mean:af1,cov:af1,max:af1,p95:af1,p99.9:e,mdtm:af1,score,...]
                         [--keys base|tempo-all-leaders] [--gpus G] [--rank-begin B --rank-end E]
+                        [--pinned a,b | --pinned 3,9]
 """
 from __future__ import annotations
 
@@ -154,6 +155,29 @@ def _objectives(spec: str):
     return out
 
 
+def _pinned(spec: Optional[str], names: Sequence[str]) -> Optional[List[int]]:
+    """--pinned: comma-separated region names or positions into the server list
+    (the planet's regions in name order), as --config takes names for `stats`."""
+    if not spec:
+        return None
+    names = list(names)
+    out = []
+    for item in spec.split(","):
+        item = item.strip()
+        if item.isdigit():
+            pos = int(item)
+            if pos >= len(names):
+                raise ValueError(f"--pinned: position {pos} is outside the {len(names)} servers")
+        elif item in names:
+            pos = names.index(item)
+        else:
+            raise ValueError(f"--pinned: unknown region {item!r}")
+        if pos in out:
+            raise ValueError(f"--pinned: {item!r} is given twice")
+        out.append(pos)
+    return out
+
+
 def sweep(args, out=sys.stdout) -> dict:
     """The exhaustive sweep of every n-subset (search.rs:199-319 + the ranking's
     compute_score, search.rs:421-472) streamed through the device top-K, sharded
@@ -168,7 +192,11 @@ def sweep(args, out=sys.stdout) -> dict:
     srv = np.arange(planet.R, dtype=np.uint32)
     objs = _objectives(args.objectives)
     keys = _lib.KEYS_TEMPO_ALL_LEADERS if args.keys == "tempo-all-leaders" else _lib.KEYS_BASE
-    total = _lib.binomial(planet.R, args.n)
+    pinned = _pinned(getattr(args, "pinned", None), planet.names)
+    if pinned is not None and (args.gpus > 1 or keys != _lib.KEYS_BASE):
+        raise ValueError("--pinned sweeps run on one device with the base key set")
+    # (--rank-begin / --rank-end of a pinned sweep are pinned ranks)
+    total = _lib.binomial(planet.R, args.n) if pinned is None else _lib.pinned_total(planet.R, args.n, len(pinned))
     rb = args.rank_begin or 0
     re = total if args.rank_end is None else args.rank_end
     if args.gpus > 1:
@@ -179,7 +207,7 @@ def sweep(args, out=sys.stdout) -> dict:
         res = h.result()
     else:
         sw = Sweep(DevicePlanet(planet, args.device), srv, srv, args.n, objs, K=args.K, ranking=DEFAULT_RANKING,
-                   digest=True, keys=keys)
+                   digest=True, keys=keys, pinned=pinned)
         sw.launch(rb, re)
         res = sw.result()
 
@@ -205,6 +233,8 @@ def sweep(args, out=sys.stdout) -> dict:
            "objectives": [{"objective": _objective_name(k) + ("" if k == _lib.OBJ_SCORE else ":" + _lib.SLOT_NAMES_X[s]),
                            "top": [record(k, s, key, rank) for key, rank in res.tops[o][:args.show]]}
                           for o, (k, s) in enumerate(objs)]}
+    if pinned is not None:
+        doc["pinned"] = pinned
     print(json.dumps(doc, indent=None if args.compact else 1), file=out)
     return doc
 
@@ -255,6 +285,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--rank-begin", type=int, default=None)
     p.add_argument("--rank-end", type=int, default=None)
+    p.add_argument("--pinned", default=None,
+                   help="region names or positions every swept config contains (rank flags are then pinned ranks)")
     p.add_argument("--compact", action="store_true")
     return ap
 

@@ -16,6 +16,7 @@
 #include "../../include/bote_hip.h"
 #include "bote_host.hpp"
 #include "bote_kernels.hpp"
+#include "bote_pinned.hpp"
 
 namespace bote {
 namespace capi __attribute__((visibility("hidden"))) {
@@ -173,6 +174,10 @@ struct bote_sweep {
   // Decided by sweep_plan_fast; bote_sweep_is_fast reports its value.
   enum class Path { Generic = 0, Fast = 1, Group = 2 };
   const bote_planet* p = nullptr;
+  // the planet's device, kept here: bote_sweep_destroy may run after the
+  // planet is gone (a garbage collector finalises the two in any order) and
+  // must not read through `p`
+  int device = 0;
   uint32_t n = 0, ns = 0, nc = 0, n_obj = 0, K = 0;
   bote::EvalArgs args{};
   uint32_t grid = 0, bd = 0;
@@ -212,6 +217,10 @@ struct bote_sweep {
   // walk across its shards' sweeps)
   mutable std::vector<std::shared_ptr<const bote::host::GroupWalk>> walks;
   DBuf wctr;
+  // a pinned sweep (bote_sweep_create_pinned; pin_n == 0: none): the sorted
+  // pinned positions and its rank space C(ns - pin_n, n - pin_n)
+  bote::PinArgs pz{};
+  uint64_t ptotal = 0;
   uint64_t last_rb = 0, last_re = 0;
   hipStream_t last_stream = nullptr;
   uint64_t result_bytes() const { return (uint64_t)n_obj * bote::KP * 16 + 16; }

@@ -101,7 +101,9 @@ static int sweep_upload_lists(bote_sweep* s, const uint32_t* servers, const uint
   s->shm = bote::eval_smem_bytes(a, n, s->bd, true);
   a.out_top = nullptr;
   if (s->shm > device_max_lds(p->device)) return fail(BOTE_E_RANGE, "planet/client set too large for LDS");
-  int nb = bote::eval_occupancy(n, false, s->bd, s->shm, keys != 0, bote::eval_passes(a.obj_kind, (int)n_obj));
+  const int passes = bote::eval_passes(a.obj_kind, (int)n_obj);
+  int nb = s->pz.pin_n ? bote::eval_pinned_occupancy(n, s->bd, s->shm, passes)
+                       : bote::eval_occupancy(n, false, s->bd, s->shm, keys != 0, passes);
   s->grid = (uint32_t)(device_cus(p->device) * nb);
   s->xgrid = 32;
   return BOTE_OK;
@@ -173,7 +175,7 @@ static int sweep_plan_group(bote_sweep* s, const FastLimits& lim, bool compiled_
   bote::FastArgs& f = s->fargs;
   // (a MAX, percentile or MDTM objective: the fast kernel's variant, s->tail; a
   // forced group kernel was refused with the arguments, check_sweep_args)
-  bool want_group = n >= 4 && ns <= 256 && group_utilisation(ns, n) >= 0.9 && !s->tail;
+  bool want_group = n >= 4 && ns <= 256 && group_utilisation(ns, n) >= 0.9 && !s->tail && !s->pz.pin_n;
   if (kernel != BOTE_KERNEL_AUTO) want_group = n >= 4 && ns <= 256 && kernel == BOTE_KERNEL_GROUP;
   if (kernel == BOTE_KERNEL_GROUP && !want_group) return fail(BOTE_E_ARG, "group kernel needs n >= 4");
   if (s->path == Path::Generic || !want_group) return BOTE_OK;
@@ -314,6 +316,14 @@ static int sweep_plan_fast(bote_sweep* s, const uint32_t* servers, const uint32_
   }
   const bool mdtm_mixed = mdtm && s->tail != bote::FAST_PLAIN;
   if (mdtm) s->tail = bote::FAST_MDTM;
+  // a pinned sweep: the fast kernel's pinned variant computes SCORE, MEAN and
+  // COV objectives; every other sweep of pinned members runs the generic
+  // kernel's pinned variant (launch_sweep_eval)
+  if (s->pz.pin_n && s->tail != bote::FAST_PLAIN && s->path != Path::Generic) {
+    if (kernel == BOTE_KERNEL_FAST)
+      return fail(BOTE_E_ARG, "the fast kernel's pinned variant computes SCORE, MEAN and COV objectives (generic kernel)");
+    s->path = Path::Generic;
+  }
   const FastLimits lim = fast_limits(p->lat.data(), p->R, nc, n);
   if (keys && eligible &&
       (!bote::group_supports_keys(n, bote::GROUP_XK_MAX_BD) || !compiled_objs || !lim.keys32 ||
@@ -357,7 +367,8 @@ static int sweep_plan_fast(bote_sweep* s, const uint32_t* servers, const uint32_
   if (s->fshm > device_max_lds(p->device)) {
     s->path = Path::Generic;
   } else {
-    s->fgrid = (uint32_t)(device_cus(p->device) * bote::fast_occupancy(n, s->tail, s->fshm));
+    s->fgrid = (uint32_t)(device_cus(p->device) * (s->pz.pin_n ? bote::fast_pinned_occupancy(n, s->fshm)
+                                                              : bote::fast_occupancy(n, s->tail, s->fshm)));
   }
   if ((rc = sweep_plan_group(s, lim, compiled_objs, kernel))) return rc;
   // the fast (non-group) kernel does not compute the extended key set
@@ -388,14 +399,17 @@ static int sweep_alloc_workspace(bote_sweep* s) {
   return BOTE_OK;
 }
 
-int bote_sweep_create_keys(const bote_planet* p, const uint32_t* servers, uint32_t ns, const uint32_t* clients,
-                           uint32_t nc, uint32_t n, const bote_objective* objs, uint32_t n_obj, uint32_t K,
-                           const bote_ranking_params* rp, int digest, int kernel, uint32_t keys, bote_sweep** out) {
+// bote_sweep_create_keys and, with `is_pinned`, bote_sweep_create_pinned
+static int sweep_create(const bote_planet* p, const uint32_t* servers, uint32_t ns, const uint32_t* clients,
+                        uint32_t nc, uint32_t n, const bote_objective* objs, uint32_t n_obj, uint32_t K,
+                        const bote_ranking_params* rp, int digest, int kernel, uint32_t keys, bool is_pinned,
+                        const uint32_t* pinned, uint32_t n_pinned, bote_sweep** out) {
   DevGuard dev_guard;  // the caller's current device is restored on return
   int rc;
   bool has_score = false;
   if (!out) return fail(BOTE_E_ARG, "out is null");
   ARG_TRY(check_sweep_args(p ? p->R : 0, servers, ns, clients, nc, n, objs, n_obj, K, rp, kernel, keys, has_score));
+  if (is_pinned) ARG_TRY(check_pinned_args(ns, n, pinned, n_pinned, kernel, keys));
   HIP_TRY(hipSetDevice(p->device));
   auto* s = new bote_sweep();
   auto cleanup = [&](int code) {
@@ -403,17 +417,55 @@ int bote_sweep_create_keys(const bote_planet* p, const uint32_t* servers, uint32
     return code;
   };
   s->p = p;
+  s->device = p->device;
   s->n = n;
   s->ns = ns;
   s->nc = nc;
   s->n_obj = n_obj;
   s->K = K;
+  if (is_pinned) {
+    s->pz.pin_n = n_pinned;
+    std::copy(pinned, pinned + n_pinned, s->pz.pin);
+    std::sort(s->pz.pin, s->pz.pin + n_pinned);
+    s->ptotal = pinned_total(ns, n, n_pinned);
+  }
   if ((rc = sweep_upload_lists(s, servers, clients, objs, rp, has_score, digest, keys))) return cleanup(rc);
   const bool fair = has_score && rp && rp->min_fairness_fpaxos_improv != 0.0;
   if ((rc = sweep_plan_fast(s, servers, clients, fair, kernel))) return cleanup(rc);
   if ((rc = sweep_alloc_workspace(s))) return cleanup(rc);
   *out = s;
   return BOTE_OK;
+}
+
+int bote_sweep_create_keys(const bote_planet* p, const uint32_t* servers, uint32_t ns, const uint32_t* clients,
+                           uint32_t nc, uint32_t n, const bote_objective* objs, uint32_t n_obj, uint32_t K,
+                           const bote_ranking_params* rp, int digest, int kernel, uint32_t keys, bote_sweep** out) {
+  return sweep_create(p, servers, ns, clients, nc, n, objs, n_obj, K, rp, digest, kernel, keys, false, nullptr, 0, out);
+}
+
+int bote_sweep_create_pinned(const bote_planet* p, const uint32_t* servers, uint32_t ns, const uint32_t* clients,
+                             uint32_t nc, uint32_t n, const uint32_t* pinned, uint32_t n_pinned,
+                             const bote_objective* objs, uint32_t n_obj, uint32_t K, const bote_ranking_params* rp,
+                             int digest, int kernel, bote_sweep** out) {
+  return sweep_create(p, servers, ns, clients, nc, n, objs, n_obj, K, rp, digest, kernel, 0, true, pinned, n_pinned,
+                      out);
+}
+
+uint64_t bote_pinned_total(uint32_t ns, uint32_t n, uint32_t n_pinned) { return pinned_total(ns, n, n_pinned); }
+
+int bote_pinned_config(uint64_t pinned_rank, uint32_t n, uint32_t ns, const uint32_t* pinned, uint32_t n_pinned,
+                       uint32_t* out_positions, uint64_t* out_rank) {
+  if (!pinned || !out_positions) return fail(BOTE_E_ARG, "null argument");
+  if (n > BOTE_MAX_N) return fail(BOTE_E_RANGE, "config size above 16");
+  if (!pinned_config(pinned_rank, n, ns, pinned, n_pinned, out_positions, out_rank))
+    return fail(BOTE_E_ARG, "bad pinned list or pinned rank out of range");
+  return BOTE_OK;
+}
+
+// the rank space of a sweep's launches: C(ns, n), or a pinned sweep's pinned ranks
+static Status sweep_rank_span(const bote_sweep* s, uint64_t rank_begin, uint64_t rank_end) {
+  return s->pz.pin_n ? check_rank_span_total(s->ptotal, rank_begin, rank_end)
+                     : check_rank_span(s->ns, s->n, rank_begin, rank_end);
 }
 
 int bote_sweep_is_fast(const bote_sweep* s, int* out) {
@@ -440,7 +492,7 @@ int bote_sweep_split(const bote_sweep* s, uint64_t rank_begin, uint64_t rank_end
                      uint64_t* out_bounds) {
   if (!s || !out_bounds) return fail(BOTE_E_ARG, "null argument");
   if (parts == 0) return fail(BOTE_E_ARG, "parts must be >= 1");
-  ARG_TRY(check_rank_span(s->ns, s->n, rank_begin, rank_end));
+  ARG_TRY(sweep_rank_span(s, rank_begin, rank_end));
   std::vector<uint64_t> b;
   if (rank_end - rank_begin >= (uint64_t)parts * 64) {
     if (auto w = walk_for(s, rank_begin, rank_end)) b = cut_chunks(*w, rank_begin, rank_end, parts);
@@ -565,6 +617,16 @@ static int timing_slot(bote_sweep* s, hipEvent_t*& e0, hipEvent_t*& e1) {
   return BOTE_OK;
 }
 
+// The generic kernel's top-K launch with `a` on the sweep's grid (a pinned
+// sweep: its pinned variant, [a.rb, a.re) being pinned ranks)
+static hipError_t launch_sweep_eval(const bote_sweep* s, const EvalArgs& a, hipStream_t st) {
+  if (!s->pz.pin_n) return bote::launch_eval(a, s->n, false, s->grid, s->bd, s->shm, st);
+  bote::PinEvalArgs pa{};
+  static_cast<EvalArgs&>(pa) = a;
+  pa.pz = s->pz;
+  return bote::launch_eval_pinned(pa, s->n, s->grid, s->bd, s->shm, st);
+}
+
 // Generic kernel over [rb, re): the exact path for any planet.
 static int launch_generic(bote_sweep* s, uint64_t rb, uint64_t re, hipStream_t st, bool timed) {
   EvalArgs a = s->args;
@@ -578,7 +640,7 @@ static int launch_generic(bote_sweep* s, uint64_t rb, uint64_t re, hipStream_t s
   s->last0 = e0 ? *e0 : s->ev0;
   s->last1 = e1 ? *e1 : s->ev1;
   HIP_TRY(hipEventRecord(s->last0, st));
-  HIP_TRY(bote::launch_eval(a, s->n, false, s->grid, s->bd, s->shm, st));
+  HIP_TRY(launch_sweep_eval(s, a, st));
   HIP_TRY(hipEventRecord(s->last1, st));
   return merge_chain(s, s->grid, st);
 }
@@ -678,7 +740,12 @@ static int launch_fast_path(bote_sweep* s, uint64_t rb, uint64_t re, hipStream_t
   s->last0 = *e0;
   s->last1 = *e1;
   if (group) HIP_TRY(bote::launch_group(f, s->n, s->def_obj, s->fgrid, s->fshm, st, *e0, *e1));
-  else HIP_TRY(bote::launch_fast(f, s->n, s->tail, s->fgrid, s->fshm, st, *e0, *e1));
+  else if (s->pz.pin_n) {
+    bote::PinFastArgs pf{};
+    static_cast<bote::FastArgs&>(pf) = f;
+    pf.pz = s->pz;
+    HIP_TRY(bote::launch_fast_pinned(pf, s->n, s->fgrid, s->fshm, st, *e0, *e1));
+  } else HIP_TRY(bote::launch_fast(f, s->n, s->tail, s->fgrid, s->fshm, st, *e0, *e1));
   // exact fixup of the deferred configs: generic kernel over the rank list
   EvalArgs a = s->args;
   a.rank_list = s->queue.as<uint64_t>();
@@ -700,14 +767,14 @@ static int launch_fast_path(bote_sweep* s, uint64_t rb, uint64_t re, hipStream_t
   g.out_counters = s->counters_alt.as<unsigned long long>();
   g.run_if_over = s->qcount.as<unsigned long long>();
   g.over_cap = QUEUE_CAP;
-  HIP_TRY(bote::launch_eval(g, s->n, false, s->grid, s->bd, s->shm, st));
+  HIP_TRY(launch_sweep_eval(s, g, st));
   return merge_chain(s, s->fgrid + s->xgrid, st, s->qcount.as<unsigned long long>(), s->grid, f.kbound);
 }
 
 int bote_sweep_launch(bote_sweep* s, uint64_t rank_begin, uint64_t rank_end, void* hip_stream) {
   DevGuard dev_guard;  // the caller's current device is restored on return
   if (!s) return fail(BOTE_E_ARG, "sweep is null");
-  ARG_TRY(check_rank_span(s->ns, s->n, rank_begin, rank_end));
+  ARG_TRY(sweep_rank_span(s, rank_begin, rank_end));
   HIP_TRY(hipSetDevice(s->p->device));
   hipStream_t st = (hipStream_t)hip_stream;
   int rc = s->path == Path::Generic ? launch_generic(s, rank_begin, rank_end, st, true)
@@ -838,7 +905,7 @@ int bote_sweep_grid(const bote_sweep* s, uint32_t* out_grid, uint32_t* out_block
 int bote_sweep_destroy(bote_sweep* s) {
   DevGuard dev_guard;  // the caller's current device is restored on return
   if (!s) return BOTE_OK;
-  (void)hipSetDevice(s->p ? s->p->device : 0);
+  (void)hipSetDevice(s->device);  // (not s->p->device: the planet may have been destroyed first)
   // work the last launch or result copy enqueued may still run (a launch
   // without a result call): wait for it before the buffers are freed and
   // handed to the next allocation.  An event, not the caller's stream (it may

@@ -58,6 +58,33 @@ uint64_t colex_rank(const uint32_t* pos, uint32_t n) {
   return r;
 }
 
+uint64_t pinned_total(uint32_t ns, uint32_t n, uint32_t m) {
+  if (m == 0 || m >= n || n > ns) return 0;
+  return binom_u64(ns - m, n - m);
+}
+
+bool pinned_config(uint64_t pinned_rank, uint32_t n, uint32_t ns, const uint32_t* pinned, uint32_t m, uint32_t* out,
+                   uint64_t* out_rank) {
+  if (!pinned || !out || m == 0 || m >= n || n > ns) return false;
+  std::vector<uint8_t> is_pinned(ns, 0);
+  for (uint32_t i = 0; i < m; ++i) {
+    if (pinned[i] >= ns || is_pinned[pinned[i]]) return false;
+    is_pinned[pinned[i]] = 1;
+  }
+  std::vector<uint32_t> free_pos;
+  for (uint32_t x = 0; x < ns; ++x)
+    if (!is_pinned[x]) free_pos.push_back(x);
+  const uint32_t F = n - m;
+  std::vector<uint32_t> q(F);
+  if (!colex_unrank(pinned_rank, F, ns - m, q.data())) return false;
+  for (uint32_t i = 0; i < F; ++i) is_pinned[free_pos[q[i]]] = 1;  // (now: is a member)
+  uint32_t j = 0;
+  for (uint32_t x = 0; x < ns; ++x)
+    if (is_pinned[x]) out[j++] = x;
+  if (out_rank) *out_rank = colex_rank(out, n);
+  return true;
+}
+
 // Fitted per-group precompute, in wavefront steps: least squares over the
 // per-shard kernel times of scripts/shard_balance.py (profiles/r02h_*): 0.64
 // at 64 clients (n=7), 3.7 at 128 clients (n=6); a power of the client count
@@ -675,6 +702,26 @@ Status check_sweep_args(uint32_t R, const uint32_t* servers, uint32_t ns, const 
     return fail(BOTE_E_ARG, "the group kernel does not compute MDTM objectives (fast or generic kernel)");
   if (has_score && !rp) return fail(BOTE_E_ARG, "SCORE objective needs ranking params");
   if (rp) return check_ft_metric(rp->ft_metric);
+  return OK;
+}
+
+Status check_pinned_args(uint32_t ns, uint32_t n, const uint32_t* pinned, uint32_t n_pinned, int kernel,
+                         uint32_t keys) {
+  if (!pinned || n_pinned == 0) return fail(BOTE_E_ARG, "pinned list is null or empty");
+  if (n_pinned >= n) return fail(BOTE_E_ARG, "pinned members must be fewer than the config size");
+  for (uint32_t i = 0; i < n_pinned; ++i)
+    if (pinned[i] >= ns) return fail(BOTE_E_ARG, "pinned position out of range");
+  for (uint32_t i = 0; i < n_pinned; ++i)
+    for (uint32_t j = 0; j < i; ++j)
+      if (pinned[i] == pinned[j]) return fail(BOTE_E_ARG, "duplicate pinned position");
+  if (kernel == BOTE_KERNEL_GROUP)
+    return fail(BOTE_E_ARG, "the group kernel does not sweep pinned members (fast or generic kernel)");
+  if (keys) return fail(BOTE_E_ARG, "pinned sweeps compute the base key set");
+  return OK;
+}
+
+Status check_rank_span_total(uint64_t total, uint64_t rank_begin, uint64_t rank_end) {
+  if (rank_begin > rank_end || rank_end > total) return fail(BOTE_E_ARG, "rank range out of bounds");
   return OK;
 }
 

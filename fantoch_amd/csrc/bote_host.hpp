@@ -29,6 +29,21 @@ std::vector<uint64_t> binom_table(uint32_t ns, uint32_t n);
 bool colex_unrank(uint64_t rank, uint32_t n, uint32_t ns, uint32_t* out);
 uint64_t colex_rank(const uint32_t* pos, uint32_t n);
 
+// ---------------------------------------------------------- pinned sweeps --
+// A pinned sweep ranks the supersets of m pinned positions: its rank space is
+// the colex ranks of F = n - m subsets of indices into free[] (the ns - m
+// unpinned positions, ascending), the "pinned rank".  For two supersets of one
+// pinned set, pinned-rank order equals full-colex-rank order (colex compares
+// the largest differing member first, the differing members are free ones and
+// free[] is increasing), so records keep the config's full colex rank.
+// C(ns - m, n - m); 0 on overflow or unless 1 <= m < n <= ns.
+uint64_t pinned_total(uint32_t ns, uint32_t n, uint32_t m);
+// pinned rank -> the config's n ascending positions and its full colex rank.
+// `pinned`: m distinct positions < ns in any order.  False for bad sizes, a
+// bad pinned list or pinned_rank >= pinned_total.
+bool pinned_config(uint64_t pinned_rank, uint32_t n, uint32_t ns, const uint32_t* pinned, uint32_t m, uint32_t* out,
+                   uint64_t* out_rank);
+
 // ------------------------------------------------------------ group walk --
 // Colex ranks of n-subsets sharing their n - 3 largest members form one
 // contiguous "group" of C(p3, 3) ranks (bote_group.hip).  The group kernel
@@ -247,6 +262,14 @@ Status check_leaderless_args(uint32_t R, const uint32_t* servers, uint32_t ns, c
 Status check_sweep_args(uint32_t R, const uint32_t* servers, uint32_t ns, const uint32_t* clients, uint32_t nc,
                         uint32_t n, const bote_objective* objs, uint32_t n_obj, uint32_t K,
                         const bote_ranking_params* rp, int kernel, uint32_t keys, bool& has_score);
+// bote_sweep_create_pinned, after check_sweep_args.  In order: a null or empty
+// pinned list, n_pinned >= n, a position >= ns, a repeated position, a forced
+// group kernel (it does not sweep pinned members), the extended key set (the
+// entry takes none: the internal path only).
+Status check_pinned_args(uint32_t ns, uint32_t n, const uint32_t* pinned, uint32_t n_pinned, int kernel,
+                         uint32_t keys);
+// rank_begin <= rank_end <= `total` (a pinned sweep's pinned_total).
+Status check_rank_span_total(uint64_t total, uint64_t rank_begin, uint64_t rank_end);
 // bote_evolving_chains' six levels (n = 3, 5, .., 13): arrays present where a
 // level has entries, every mask an n-subset of the ns servers.
 Status check_chain_levels(uint32_t ns, const uint32_t* counts, const uint64_t* const* masks,

@@ -21,7 +21,10 @@
 //                          (permutator combination -> colex ranks)
 //   k_single_*             Bote::{leaderless, leader, all_leaders_stats, best_leader}
 #include "bote_kernels.hpp"
+#include <type_traits>
+
 #include "bote_launch.hpp"
+#include "bote_pinned.hpp"
 
 namespace bote {
 
@@ -611,8 +614,13 @@ __device__ __forceinline__ void eval_config(const EvalArgs& a, const Smem& s, co
 }
 
 // ------------------------------------------------------------ the kernel --
-template <int N, bool FULL, bool X, int PASSES = EVAL_PLAIN>
-__global__ void __launch_bounds__(256) eval_kernel(EvalArgs a) {
+// PIN: the pinned variant (bote_pinned.hpp; top-K sweeps of the base key set in
+// the rank-range mode).  [rb, re) are pinned ranks: a lane unranks the free
+// indices q of its first one, walks `runlen` successors and merges the members
+// per step; the digest and the records carry the full colex rank.
+template <int N, bool FULL, bool X, int PASSES = EVAL_PLAIN, bool PIN = false>
+__global__ void __launch_bounds__(256) eval_kernel(std::conditional_t<PIN, PinEvalArgs, EvalArgs> a) {
+  static_assert(!PIN || (!FULL && !X), "the pinned variant is a top-K sweep of the base key set");
   constexpr bool PCTL = PASSES >= EVAL_PCTL;
   static_assert(!(FULL && PCTL), "percentile and MDTM objectives belong to top-K sweeps");
   constexpr int NLW = (QTab<N, X>::NT + 1) / 2;
@@ -676,7 +684,12 @@ __global__ void __launch_bounds__(256) eval_kernel(EvalArgs a) {
 #pragma unroll
     for (int j = 0; j < N; ++j) p[j] = j;
     uint64_t rend = a.re;
-    if (jobok) {
+    [[maybe_unused]] uint32_t q[PIN ? N : 1];  // PIN: the free indices
+    if constexpr (PIN) {
+#pragma unroll
+      for (int j = 0; j < N; ++j) q[j] = 0;
+      if (jobok) pin_unrank<N>(s.binom, a.ns, a.pz, rank, q);
+    } else if (jobok) {
       if (a.cfgs) {
 #pragma unroll
         for (int j = 0; j < N; ++j) p[j] = a.cfgs[rank * N + j];
@@ -690,6 +703,10 @@ __global__ void __launch_bounds__(256) eval_kernel(EvalArgs a) {
     }
     for (uint64_t t = 0; t < runlen; ++t) {
       const bool have = jobok && rank < rend;
+      uint64_t frank = rank;  // the config's full colex rank (PIN: `rank` is the pinned rank)
+      if constexpr (PIN) {
+        if (have) pin_members<N>(s.binom, a.pz, q, p, frank);
+      }
       CfgOut<N, X, PASSES> r;
       if (have) {
         eval_config<N, FULL, X, PASSES>(a, s, p, sorted_in, rank - a.rb, r);
@@ -710,7 +727,7 @@ __global__ void __launch_bounds__(256) eval_kernel(EvalArgs a) {
             for (int sl = 10; sl < 20; ++sl)
               if (slot_has<N>(sl)) h = digest_fold(h, sl, r.mom[sl].s1, r.mom[sl].s2);
           }
-          digest += digest_final(rank, r.lead_orig, h);
+          digest += digest_final(frank, r.lead_orig, h);
         }
         if (FULL) {
           const uint64_t oi = rank - a.rb;
@@ -768,9 +785,13 @@ __global__ void __launch_bounds__(256) eval_kernel(EvalArgs a) {
             }
           }
         }
-        topk_step(s.tk, a.n_obj, a.K, key, ok, rank);
+        topk_step(s.tk, a.n_obj, a.K, key, ok, frank);
       }
-      if (have && !a.cfgs) colex_next<N>(a.ns, p);
+      if constexpr (PIN) {
+        if (have) pin_next<N>(a.ns, a.pz, q);
+      } else {
+        if (have && !a.cfgs) colex_next<N>(a.ns, p);
+      }
       ++rank;
     }
   }
@@ -925,6 +946,33 @@ hipError_t launch_eval(const EvalArgs& a, uint32_t n, bool full, uint32_t grid, 
                        hipStream_t st) {
   // a percentile or MDTM objective among a top-K sweep's (bote_kernels.hpp EVAL_*)
   const void* k = eval_fn(n, full, a.keys != 0, full ? (int)EVAL_PLAIN : eval_passes(a.obj_kind, a.n_obj));
+  return k ? launch_kernel(k, a, grid, bd, shm, st) : hipErrorInvalidValue;
+}
+
+// ---- the pinned variant (bote_pinned.hpp): EVAL_PLAIN, or EVAL_MDTM for a
+// sweep with a percentile or an MDTM objective (each level has the passes of
+// the ones below it); one selector for the occupancy query and the launch
+static const void* eval_pinned_fn(uint32_t n, int passes) {
+  switch (n) {
+#define FN_CASE(NN)                                                                                   \
+  case NN:                                                                                            \
+    return passes != EVAL_PLAIN ? (const void*)eval_kernel<NN, false, false, EVAL_MDTM, true>         \
+                                : (const void*)eval_kernel<NN, false, false, EVAL_PLAIN, true>;
+    FN_CASE(2) FN_CASE(3) FN_CASE(4) FN_CASE(5) FN_CASE(6) FN_CASE(7) FN_CASE(8) FN_CASE(9)
+    FN_CASE(10) FN_CASE(11) FN_CASE(12) FN_CASE(13) FN_CASE(14) FN_CASE(15) FN_CASE(16)
+#undef FN_CASE
+    default: return nullptr;
+  }
+}
+
+int eval_pinned_occupancy(uint32_t n, uint32_t bd, size_t shm, int passes) {
+  const void* k = eval_pinned_fn(n, passes);
+  return k ? kernel_occupancy(k, bd, shm, 1) : 0;
+}
+
+hipError_t launch_eval_pinned(const PinEvalArgs& a, uint32_t n, uint32_t grid, uint32_t bd, size_t shm,
+                              hipStream_t st) {
+  const void* k = eval_pinned_fn(n, eval_passes(a.obj_kind, a.n_obj));
   return k ? launch_kernel(k, a, grid, bd, shm, st) : hipErrorInvalidValue;
 }
 

@@ -24,7 +24,10 @@
 // Input leaderless keys by the packed client-quad loop; compute_score validity
 // by integer / f64-margin decisions; digest; block top-K.
 #include "bote_fast.hpp"
+#include <type_traits>
+
 #include "bote_launch.hpp"
+#include "bote_pinned.hpp"
 
 
 namespace bote {
@@ -414,8 +417,15 @@ __device__ __forceinline__ uint64_t small_mdtm_h(const uint32_t (&x)[N], uint32_
 // loop's values again, both in registers (small_mdtm_h).  Each H goes into its
 // objectives' keys at once, before finish_config, which leaves them alone;
 // they are withdrawn when it defers the config.
-template <int N, int TAIL>
-__global__ void __launch_bounds__(FAST_BD, 4) sweep_fast_kernel(FastArgs a) {
+// PIN: the pinned variant (bote_pinned.hpp; FAST_PLAIN only).  [rb, re) are
+// pinned ranks; a lane walks `runlen` of them over the free indices q and
+// re-merges the members per step.  The full colex rank is computed with the
+// members, always: the digest, a record offered to the top-K and a deferred
+// config's queue entry carry it, and everything after p[N] is the code of the
+// unpinned kernel.
+template <int N, int TAIL, bool PIN = false>
+__global__ void __launch_bounds__(FAST_BD, 4) sweep_fast_kernel(std::conditional_t<PIN, PinFastArgs, FastArgs> a) {
+  static_assert(!PIN || TAIL == FAST_PLAIN, "the pinned variant computes SCORE, MEAN and COV objectives");
   using QC = QCfg<N>;
   constexpr int NL = QC::NL;
   constexpr int NLW = NL <= 2 ? 1 : 2;
@@ -521,9 +531,20 @@ __global__ void __launch_bounds__(FAST_BD, 4) sweep_fast_kernel(FastArgs a) {
     uint32_t p[N];
 #pragma unroll
     for (int j = 0; j < N; ++j) p[j] = j;
-    if (jobok) colex_unrank<N>(s.binom, a.ns, rank, p);
+    [[maybe_unused]] uint32_t q[PIN ? N : 1];  // PIN: the free indices (one unused word otherwise)
+    if constexpr (PIN) {
+#pragma unroll
+      for (int j = 0; j < N; ++j) q[j] = 0;
+      if (jobok) pin_unrank<N>(s.binom, a.ns, a.pz, rank, q);
+    } else {
+      if (jobok) colex_unrank<N>(s.binom, a.ns, rank, p);
+    }
     for (uint64_t tt = 0; tt < runlen; ++tt) {
       bool have = jobok && rank < a.re;
+      uint64_t frank = rank;  // the config's full colex rank (PIN: `rank` is the pinned rank)
+      if constexpr (PIN) {
+        if (have) pin_members<N>(s.binom, a.pz, q, p, frank);
+      }
       uint64_t key[MAXOBJ];
       bool ok[MAXOBJ];
 #pragma unroll
@@ -611,7 +632,7 @@ __global__ void __launch_bounds__(FAST_BD, 4) sweep_fast_kernel(FastArgs a) {
           }
         }
         if (amb) {  // defer to the exact generic kernel (see bote_sweep_launch)
-          defer_rank(a, rank);
+          defer_rank(a, frank);
           have = false;
         }
         if (have) {
@@ -810,9 +831,9 @@ __global__ void __launch_bounds__(FAST_BD, 4) sweep_fast_kernel(FastArgs a) {
               }
             }
           }
-          if (!finish_config<N, TAIL>(a, mom, s.vcol[lp], bi, rank, s.tk.thr, pnc1, pnc2, valid_cnt, digest, key,
+          if (!finish_config<N, TAIL>(a, mom, s.vcol[lp], bi, frank, s.tk.thr, pnc1, pnc2, valid_cnt, digest, key,
                                       ok)) {
-            defer_rank(a, rank);
+            defer_rank(a, frank);
             have = false;
             if constexpr (TAIL) {
 #pragma unroll
@@ -821,8 +842,12 @@ __global__ void __launch_bounds__(FAST_BD, 4) sweep_fast_kernel(FastArgs a) {
           }
         }
       }
-      if (!ABLATE(a, 4)) topk_step(s.tk, a.n_obj, a.K, key, ok, rank);
-      if (jobok && rank < a.re) colex_next<N>(a.ns, p);
+      if (!ABLATE(a, 4)) topk_step(s.tk, a.n_obj, a.K, key, ok, frank);
+      if constexpr (PIN) {
+        if (jobok && rank < a.re) pin_next<N>(a.ns, a.pz, q);
+      } else {
+        if (jobok && rank < a.re) colex_next<N>(a.ns, p);
+      }
       ++rank;
     }
   }
@@ -836,10 +861,11 @@ __global__ void __launch_bounds__(FAST_BD, 4) sweep_fast_kernel(FastArgs a) {
 // ------------------------------------------------------------- launcher ---
 // the kernel for config size n (null: unsupported), for the occupancy query
 // and the launch alike
-static const void* fast_fn(uint32_t n, int tail) {
+static const void* fast_fn(uint32_t n, int tail, bool pin = false) {
   switch (n) {
 #define FN_CASE(NN)                                                                  \
   case NN:                                                                           \
+    if (pin) return tail == FAST_PLAIN ? (const void*)sweep_fast_kernel<NN, FAST_PLAIN, true> : nullptr; \
     return tail == FAST_MDTM   ? (const void*)sweep_fast_kernel<NN, FAST_MDTM>       \
            : tail == FAST_LIST ? (const void*)sweep_fast_kernel<NN, FAST_LIST>       \
            : tail == FAST_MAX  ? (const void*)sweep_fast_kernel<NN, FAST_MAX>        \
@@ -859,6 +885,19 @@ int fast_occupancy(uint32_t n, int tail, size_t shm) {
 hipError_t launch_fast(const FastArgs& a, uint32_t n, int tail, uint32_t grid, size_t shm, hipStream_t st,
                        hipEvent_t e0, hipEvent_t e1) {
   const void* k = fast_fn(n, tail);
+  return k ? launch_kernel(k, a, grid, FAST_BD, shm, st, e0, e1) : hipErrorInvalidValue;
+}
+
+// ---- the pinned variant: the same selector, so the occupancy query and the
+// launch see the kernel that runs (its LDS is fast_smem_bytes' for FAST_PLAIN)
+int fast_pinned_occupancy(uint32_t n, size_t shm) {
+  const void* k = fast_fn(n, FAST_PLAIN, true);
+  return k ? kernel_occupancy(k, FAST_BD, shm, 1) : 0;
+}
+
+hipError_t launch_fast_pinned(const PinFastArgs& a, uint32_t n, uint32_t grid, size_t shm, hipStream_t st,
+                              hipEvent_t e0, hipEvent_t e1) {
+  const void* k = fast_fn(n, FAST_PLAIN, true);
   return k ? launch_kernel(k, a, grid, FAST_BD, shm, st, e0, e1) : hipErrorInvalidValue;
 }
 

@@ -322,6 +322,29 @@ int bote_sweep_create_keys(const bote_planet* p, const uint32_t* servers, uint32
                            const bote_objective* objs, uint32_t n_obj, uint32_t K,
                            const bote_ranking_params* rp, int digest, int kernel, uint32_t keys,
                            bote_sweep** out);
+/* bote_sweep_create_ex restricted to the supersets of `pinned`: n_pinned
+ * distinct positions into `servers`, 1 <= n_pinned < n, in any order, that
+ * every swept config contains ("we run in A, B, C: which regions do we add?").
+ * The sweep's rank space is the colex ranks of the n - n_pinned free members
+ * over the ns - n_pinned unpinned positions, ascending: the pinned rank, 0 <=
+ * pr < bote_pinned_total(ns, n, n_pinned) (bote_pinned_config maps it to the
+ * config).  bote_sweep_launch and bote_sweep_split take pinned ranks; every
+ * record, and the digest, carry the config's full colex rank, so records
+ * compare with an unpinned sweep's, bote_colex_unrank works on them, and the
+ * result blocks of pinned shards merge with bote_merge_device (for two
+ * supersets of one pinned set, pinned-rank order is full-rank order).
+ * Base key set.  Routing: AUTO or forced fast on an eligible planet with only
+ * SCORE, MEAN and COV objectives runs the fast kernel's pinned variant (its
+ * deferred configs go to the generic kernel's rank-list fix-up); AUTO with a
+ * MAX, percentile or MDTM objective, an ineligible planet, and a forced
+ * generic kernel run the generic kernel's pinned variant, as does the fast
+ * sweep's overflow fallback; a forced fast kernel with a MAX, percentile or MDTM objective
+ * and a forced group kernel are BOTE_E_ARG. */
+int bote_sweep_create_pinned(const bote_planet* p, const uint32_t* servers, uint32_t ns,
+                             const uint32_t* clients, uint32_t nc, uint32_t n,
+                             const uint32_t* pinned, uint32_t n_pinned,
+                             const bote_objective* objs, uint32_t n_obj, uint32_t K,
+                             const bote_ranking_params* rp, int digest, int kernel, bote_sweep** out);
 /* Asynchronous on `hip_stream`: the sweep kernel, the exact fix-up of its
  * deferred near-tie configs, the (device-decided) overflow fallback and the
  * merge chain are all stream-ordered; no host synchronisation. */
@@ -366,6 +389,8 @@ int bote_sweep_split(const bote_sweep* s, uint64_t rank_begin, uint64_t rank_end
 int bote_sweep_deferred(bote_sweep* s, void* hip_stream, uint64_t* out);
 /* Launch geometry chosen at creation (persistent grid, block size, LDS bytes). */
 int bote_sweep_grid(const bote_sweep* s, uint32_t* out_grid, uint32_t* out_block, uint32_t* out_lds_bytes);
+/* A sweep may be destroyed after its planet (it keeps the planet's device
+ * itself); every other entry needs the planet alive. */
 int bote_sweep_destroy(bote_sweep* s);
 
 /* ------------------------------------------------ multi-device search --- */
@@ -415,6 +440,13 @@ int bote_search_topk(const bote_planet* const* planets, uint32_t n_devices,
 int bote_colex_unrank(uint64_t rank, uint32_t n, uint32_t ns, uint32_t* out_positions);
 /* C(ns, n) as uint64 (0 on overflow or n > ns). */
 uint64_t bote_binomial(uint32_t ns, uint32_t n);
+/* C(ns - n_pinned, n - n_pinned): a pinned sweep's rank space; 0 on overflow
+ * or bad sizes (host only). */
+uint64_t bote_pinned_total(uint32_t ns, uint32_t n, uint32_t n_pinned);
+/* pinned rank -> the config's n ascending positions and its full colex rank
+ * (host only; out_rank may be null). */
+int bote_pinned_config(uint64_t pinned_rank, uint32_t n, uint32_t ns, const uint32_t* pinned,
+                       uint32_t n_pinned, uint32_t* out_positions, uint64_t* out_rank);
 /* Histogram::percentile's index arithmetic for p = bp / 10000.0 over `count`
  * values (host only): *out_idx = round(p * count), *out_whole = 1 when
  * p * count is that integer exactly (the percentile is then the midpoint of

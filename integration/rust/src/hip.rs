@@ -151,6 +151,14 @@ extern "C" {
     pub fn bote_colex_unrank(rank: u64, n: u32, ns: u32, out_positions: *mut u32) -> c_int;
     pub fn bote_binomial(ns: u32, n: u32) -> u64;
     pub fn bote_percentile_index(bp: u32, count: u32, out_idx: *mut u32, out_whole: *mut c_int) -> c_int;
+    pub fn bote_pinned_total(ns: u32, n: u32, n_pinned: u32) -> u64;
+    pub fn bote_pinned_config(pinned_rank: u64, n: u32, ns: u32, pinned: *const u32, n_pinned: u32,
+                              out_positions: *mut u32, out_rank: *mut u64) -> c_int;
+    pub fn bote_sweep_create_pinned(p: *const bote_planet, servers: *const u32, ns: u32, clients: *const u32,
+                                    nc: u32, n: u32, pinned: *const u32, n_pinned: u32,
+                                    objs: *const bote_objective, n_obj: u32, k: u32,
+                                    rp: *const bote_ranking_params, digest: c_int, kernel: c_int,
+                                    out: *mut *mut bote_sweep) -> c_int;
 }
 
 /// Turns a status code into the panic the reference raises at the same place
