@@ -102,8 +102,7 @@ static int sweep_upload_lists(bote_sweep* s, const uint32_t* servers, const uint
   a.out_top = nullptr;
   if (s->shm > device_max_lds(p->device)) return fail(BOTE_E_RANGE, "planet/client set too large for LDS");
   const int passes = bote::eval_passes(a.obj_kind, (int)n_obj);
-  int nb = s->pz.pin_n ? bote::eval_pinned_occupancy(n, s->bd, s->shm, passes)
-                       : bote::eval_occupancy(n, false, s->bd, s->shm, keys != 0, passes);
+  int nb = bote::eval_occupancy(n, false, s->bd, s->shm, keys != 0, passes, s->pz.pin_n != 0);
   s->grid = (uint32_t)(device_cus(p->device) * nb);
   s->xgrid = 32;
   return BOTE_OK;
@@ -367,8 +366,7 @@ static int sweep_plan_fast(bote_sweep* s, const uint32_t* servers, const uint32_
   if (s->fshm > device_max_lds(p->device)) {
     s->path = Path::Generic;
   } else {
-    s->fgrid = (uint32_t)(device_cus(p->device) * (s->pz.pin_n ? bote::fast_pinned_occupancy(n, s->fshm)
-                                                              : bote::fast_occupancy(n, s->tail, s->fshm)));
+    s->fgrid = (uint32_t)(device_cus(p->device) * bote::fast_occupancy(n, s->tail, s->pz.pin_n != 0, s->fshm));
   }
   if ((rc = sweep_plan_group(s, lim, compiled_objs, kernel))) return rc;
   // the fast (non-group) kernel does not compute the extended key set
@@ -620,11 +618,7 @@ static int timing_slot(bote_sweep* s, hipEvent_t*& e0, hipEvent_t*& e1) {
 // The generic kernel's top-K launch with `a` on the sweep's grid (a pinned
 // sweep: its pinned variant, [a.rb, a.re) being pinned ranks)
 static hipError_t launch_sweep_eval(const bote_sweep* s, const EvalArgs& a, hipStream_t st) {
-  if (!s->pz.pin_n) return bote::launch_eval(a, s->n, false, s->grid, s->bd, s->shm, st);
-  bote::PinEvalArgs pa{};
-  static_cast<EvalArgs&>(pa) = a;
-  pa.pz = s->pz;
-  return bote::launch_eval_pinned(pa, s->n, s->grid, s->bd, s->shm, st);
+  return bote::launch_eval(a, s->n, false, s->grid, s->bd, s->shm, st, s->pz.pin_n ? &s->pz : nullptr);
 }
 
 // Generic kernel over [rb, re): the exact path for any planet.
@@ -740,12 +734,7 @@ static int launch_fast_path(bote_sweep* s, uint64_t rb, uint64_t re, hipStream_t
   s->last0 = *e0;
   s->last1 = *e1;
   if (group) HIP_TRY(bote::launch_group(f, s->n, s->def_obj, s->fgrid, s->fshm, st, *e0, *e1));
-  else if (s->pz.pin_n) {
-    bote::PinFastArgs pf{};
-    static_cast<bote::FastArgs&>(pf) = f;
-    pf.pz = s->pz;
-    HIP_TRY(bote::launch_fast_pinned(pf, s->n, s->fgrid, s->fshm, st, *e0, *e1));
-  } else HIP_TRY(bote::launch_fast(f, s->n, s->tail, s->fgrid, s->fshm, st, *e0, *e1));
+  else HIP_TRY(bote::launch_fast(f, s->n, s->tail, s->pz.pin_n ? &s->pz : nullptr, s->fgrid, s->fshm, st, *e0, *e1));
   // exact fixup of the deferred configs: generic kernel over the rank list
   EvalArgs a = s->args;
   a.rank_list = s->queue.as<uint64_t>();

@@ -915,13 +915,20 @@ size_t eval_smem_bytes(const EvalArgs& a, uint32_t n, uint32_t bd, bool topk) {
 }
 
 // the kernel for config size n, full outputs or top-K, base or extended keys
-// (null: unsupported n), for the occupancy query and the launch alike
+// (null: unsupported), for the occupancy query and the launch alike
 // `passes` (EVAL_*): the top-K instantiation that also computes percentile
 // objectives, or those and MDTM objectives
-static const void* eval_fn(uint32_t n, bool full, bool keys, int passes) {
+// `pin`: the pinned variant (bote_pinned.hpp; top-K, base keys): EVAL_PLAIN, or
+// EVAL_MDTM for a sweep with a percentile or an MDTM objective (each level has
+// the passes of the ones below it)
+static const void* eval_fn(uint32_t n, bool full, bool keys, int passes, bool pin) {
+  if (pin && (full || keys)) return nullptr;
   switch (n) {
 #define FN_CASE(NN)                                                                                             \
   case NN:                                                                                                      \
+    if (pin)                                                                                                    \
+      return passes != EVAL_PLAIN ? (const void*)eval_kernel<NN, false, false, EVAL_MDTM, true>                 \
+                                  : (const void*)eval_kernel<NN, false, false, EVAL_PLAIN, true>;               \
     if (passes >= EVAL_MDTM && !full)                                                                           \
       return keys ? (const void*)eval_kernel<NN, false, true, EVAL_MDTM>                                        \
                   : (const void*)eval_kernel<NN, false, false, EVAL_MDTM>;                                      \
@@ -937,43 +944,22 @@ static const void* eval_fn(uint32_t n, bool full, bool keys, int passes) {
   }
 }
 
-int eval_occupancy(uint32_t n, bool full, uint32_t bd, size_t shm, bool keys, int passes) {
-  const void* k = eval_fn(n, full, keys, passes);
+int eval_occupancy(uint32_t n, bool full, uint32_t bd, size_t shm, bool keys, int passes, bool pin) {
+  const void* k = eval_fn(n, full, keys, passes, pin);
   return k ? kernel_occupancy(k, bd, shm, 1) : 0;
 }
 
 hipError_t launch_eval(const EvalArgs& a, uint32_t n, bool full, uint32_t grid, uint32_t bd, size_t shm,
-                       hipStream_t st) {
+                       hipStream_t st, const PinArgs* pin) {
   // a percentile or MDTM objective among a top-K sweep's (bote_kernels.hpp EVAL_*)
-  const void* k = eval_fn(n, full, a.keys != 0, full ? (int)EVAL_PLAIN : eval_passes(a.obj_kind, a.n_obj));
-  return k ? launch_kernel(k, a, grid, bd, shm, st) : hipErrorInvalidValue;
-}
-
-// ---- the pinned variant (bote_pinned.hpp): EVAL_PLAIN, or EVAL_MDTM for a
-// sweep with a percentile or an MDTM objective (each level has the passes of
-// the ones below it); one selector for the occupancy query and the launch
-static const void* eval_pinned_fn(uint32_t n, int passes) {
-  switch (n) {
-#define FN_CASE(NN)                                                                                   \
-  case NN:                                                                                            \
-    return passes != EVAL_PLAIN ? (const void*)eval_kernel<NN, false, false, EVAL_MDTM, true>         \
-                                : (const void*)eval_kernel<NN, false, false, EVAL_PLAIN, true>;
-    FN_CASE(2) FN_CASE(3) FN_CASE(4) FN_CASE(5) FN_CASE(6) FN_CASE(7) FN_CASE(8) FN_CASE(9)
-    FN_CASE(10) FN_CASE(11) FN_CASE(12) FN_CASE(13) FN_CASE(14) FN_CASE(15) FN_CASE(16)
-#undef FN_CASE
-    default: return nullptr;
-  }
-}
-
-int eval_pinned_occupancy(uint32_t n, uint32_t bd, size_t shm, int passes) {
-  const void* k = eval_pinned_fn(n, passes);
-  return k ? kernel_occupancy(k, bd, shm, 1) : 0;
-}
-
-hipError_t launch_eval_pinned(const PinEvalArgs& a, uint32_t n, uint32_t grid, uint32_t bd, size_t shm,
-                              hipStream_t st) {
-  const void* k = eval_pinned_fn(n, eval_passes(a.obj_kind, a.n_obj));
-  return k ? launch_kernel(k, a, grid, bd, shm, st) : hipErrorInvalidValue;
+  const int passes = full ? (int)EVAL_PLAIN : eval_passes(a.obj_kind, a.n_obj);
+  const void* k = eval_fn(n, full, a.keys != 0, passes, pin != nullptr);
+  if (!k) return hipErrorInvalidValue;
+  if (!pin) return launch_kernel(k, a, grid, bd, shm, st);
+  PinEvalArgs pa{};
+  static_cast<EvalArgs&>(pa) = a;
+  pa.pz = *pin;
+  return launch_kernel(k, pa, grid, bd, shm, st);
 }
 
 hipError_t launch_single(const SingleArgs& a, int mode, hipStream_t st) {

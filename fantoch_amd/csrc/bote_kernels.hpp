@@ -191,6 +191,13 @@ struct FastArgs {
   uint32_t ablate;
 #endif
 };
+// A pinned sweep's fixed members (bote_pinned.hpp).  The launchers of the fast
+// and the generic kernel take a pointer to it (null: not pinned), run their
+// pinned variant and append it to the kernel's arguments.
+struct PinArgs {
+  uint32_t pin_n;      // m
+  uint32_t pin[MAXN];  // the pinned positions, ascending; 0 from pin_n on
+};
 #ifdef BOTE_DEBUG
 // bit `code` of *dbg_flag when `cond` fails (codes: DESIGN.md §5, debug build)
 #define GASSERT(a, cond, code)                                                    \
@@ -229,10 +236,11 @@ struct FastArgs {
 // MDTM objective beside a MAX or percentile one runs the generic kernel
 enum { FAST_PLAIN = 0, FAST_MAX = 1, FAST_LIST = 2, FAST_MDTM = 3 };
 size_t fast_smem_bytes(const FastArgs& a, uint32_t n, int tail);
-int fast_occupancy(uint32_t n, int tail, size_t shm);
+// (pin: the pinned variant, FAST_PLAIN only: SCORE, MEAN and COV objectives)
+int fast_occupancy(uint32_t n, int tail, bool pin, size_t shm);
 // (e0, e1: events carried by the dispatch itself, bote_launch.hpp, for a timed launch)
-hipError_t launch_fast(const FastArgs& a, uint32_t n, int tail, uint32_t grid, size_t shm, hipStream_t st,
-                       hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
+hipError_t launch_fast(const FastArgs& a, uint32_t n, int tail, const PinArgs* pin, uint32_t grid, size_t shm,
+                       hipStream_t st, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
 size_t group_smem_bytes(const FastArgs& a, uint32_t n);
 bool group_uses_lines(uint32_t n);  // n <= 7: client lines (FastArgs::gslots) and register lookups
 // the extended key set's group kernels target BOTE_GROUP_WAVES_XK waves per
@@ -266,9 +274,14 @@ inline int eval_passes(const uint32_t* obj_kind, int n_obj) {
   return e;
 }
 // (passes: the top-K instantiation launch_eval takes for the sweep's objectives, eval_passes)
-int eval_occupancy(uint32_t n, bool full, uint32_t bd, size_t shm, bool keys = false, int passes = EVAL_PLAIN);
+// (pin: the pinned variant, a top-K sweep of the base key set in the
+// rank-range mode, [a.rb, a.re) being pinned ranks: the generic path, the fast
+// sweep's overflow fallback, and MAX / percentile / MDTM objectives.  It has
+// EVAL_PLAIN and EVAL_MDTM; a percentile sweep takes EVAL_MDTM)
+int eval_occupancy(uint32_t n, bool full, uint32_t bd, size_t shm, bool keys = false, int passes = EVAL_PLAIN,
+                   bool pin = false);
 hipError_t launch_eval(const EvalArgs& a, uint32_t n, bool full, uint32_t grid, uint32_t bd, size_t shm,
-                       hipStream_t st);
+                       hipStream_t st, const PinArgs* pin = nullptr);
 
 // ---- top-K lists: merge, seed, counters (bote_merge.hip)
 // One level of the merge tree: every G_MERGE_LISTS lists of `src` (n_lists

@@ -19,11 +19,8 @@
 
 namespace bote {
 
-struct PinArgs {
-  uint32_t pin_n;      // m
-  uint32_t pin[MAXN];  // the pinned positions, ascending; 0 from pin_n on
-};
-// The fast kernel's arguments with the pinned fields at the end: the kernarg
+// The fast kernel's arguments with the pinned fields (PinArgs,
+// bote_kernels.hpp) at the end, as its launcher builds them: the kernarg
 // offsets of FastArgs stay.
 struct PinFastArgs : FastArgs {
   PinArgs pz;
@@ -108,19 +105,5 @@ __device__ __forceinline__ void pin_members(const uint64_t* binom, const PinArgs
   }
   full_rank = r;
 }
-
-// ---- the pinned variant of the fast kernel, sweep_fast_kernel<N, FAST_PLAIN,
-// true> (bote_sweep.hip): SCORE, MEAN and COV objectives
-int fast_pinned_occupancy(uint32_t n, size_t shm);
-hipError_t launch_fast_pinned(const PinFastArgs& a, uint32_t n, uint32_t grid, size_t shm, hipStream_t st,
-                              hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
-
-// ---- the pinned variant of the generic kernel, eval_kernel<N, false, false,
-// PASSES, true> for EVAL_PLAIN and EVAL_MDTM (bote_kernels.hip), in its
-// rank-range mode: the generic path, the fast sweep's overflow fallback, and
-// MAX / percentile / MDTM objectives (a percentile sweep takes EVAL_MDTM)
-int eval_pinned_occupancy(uint32_t n, uint32_t bd, size_t shm, int passes);
-hipError_t launch_eval_pinned(const PinEvalArgs& a, uint32_t n, uint32_t grid, uint32_t bd, size_t shm,
-                              hipStream_t st);
 
 }  // namespace bote

@@ -122,14 +122,16 @@ def gcp_expected(gcp, n, objs):
 
 
 # ------------------------------------------------------------------ 1, 9 ---
-@pytest.mark.parametrize("n", [3, 5, 7, 9])
+@pytest.mark.parametrize("n", [3, 5, 7, 9, 11])
 def test_gcp_full_sweep_vs_oracle(gcp, n):
-    """GCP R=20 (nq = 5: an odd quad count), n = 3, 5, 7 (1..3 leaderless
-    tables) and 9 (the non-pipelined client loop), on auto (the MDTM variant of
-    the fast kernel), forced fast and forced generic.  n = 3 has configs with H
-    = 0 on af1C (the zero key).  Then the f64 value: 2 H / c^2 from mdtm_key
-    against the oracle's Histogram::mdtm of the record's values, within 1e-12
-    relative (the project's COV bar), and exactly 0.0 when H = 0."""
+    """GCP R=20 (nq = 5: an odd quad count), n = 3 (one leaderless table), 5, 7
+    (two), 9 (two; the non-pipelined client loop) and 11 (three: the second
+    pass's second qtab plane; the read-back of the third table is the next
+    test's), on auto (the MDTM variant of the fast kernel), forced fast and
+    forced generic.  n = 3 has configs with H = 0 on af1C (the zero key).  Then
+    the f64 value: 2 H / c^2 from mdtm_key against the oracle's Histogram::mdtm
+    of the record's values, within 1e-12 relative (the project's COV bar, DESIGN
+    §2), and exactly 0.0 when H = 0."""
     p, dp, o = gcp
     srv = np.arange(p.R, dtype=np.uint32)
     objs = objectives(n)
@@ -159,6 +161,23 @@ def test_gcp_full_sweep_vs_oracle(gcp, n):
                 worst = max(worst, abs(got - ref) / ref)
                 assert abs(got - ref) <= 1e-12 * ref, (slot, r, got, ref)
     print(f"n={n}: worst relative difference of 2H/c^2 to the oracle's mdtm {worst:.3g}")
+
+
+def test_gcp_n11_colocated_third_table_vs_oracle(gcp):
+    """At n = 11 the third leaderless table is E's, and the only slot that reads
+    its colocated values is eC (5 + E), which objectives(11) has no room for
+    (MAXOBJ): MDTM eC (the read-back of the lane's second qtab plane) beside
+    MDTM e (the second pass's second plane), on auto, forced fast and forced
+    generic."""
+    p, dp, _ = gcp
+    srv = np.arange(p.R, dtype=np.uint32)
+    objs = [(MEAN, AF1), (MDTM, 5 + E), (MDTM, E)]
+    want = gcp_expected(gcp, 11, objs)
+    assert len({k for k, _ in want[1]}) > 1  # (the eC keys tell configs apart)
+    for kernel in KERNELS:
+        sw, tops = run(dp, srv, srv, 11, objs, kernel)
+        assert sw.kernel_path() == path_of(kernel), kernel
+        assert tops == want, kernel
 
 
 # --------------------------------------------------------------------- 2 ---

@@ -32,7 +32,7 @@ KERNELS = [None, "fast", "generic"]
 
 def objectives(n):
     """needs over 20 clients: p95 2 (whole), p93 2, p85 4 (whole: the full list
-    depth), p99 1, p90 3 (whole); over the n = 3, 5, 7, 9 members: p75 2, 2, 3, 3."""
+    depth), p99 1, p90 3 (whole); over the n = 3, 5, 7, 9, 11 members: p75 2, 2, 3, 3, 4."""
     objs = [(MEAN, AF1), (P(9500), AF1), (P(9300), FF1), (P(8500), E), (P(9900), AF1), (P(7500), 5 + AF1),
             (P(7500), 5 + FF1)]
     if n // 2 >= 2:
@@ -114,11 +114,14 @@ def gcp_expected(gcp, n, objs):
 
 
 # --------------------------------------------------------------------- 1 ---
-@pytest.mark.parametrize("n", [3, 5, 7, 9])
+@pytest.mark.parametrize("n", [3, 5, 7, 9, 11])
 def test_gcp_full_sweep_vs_oracle(gcp, n):
-    """GCP R=20 (nq = 5: the pipelined pair loop with an odd quad count), n = 3,
-    5, 7 (1..3 leaderless tables) and 9 (the non-pipelined loop), on auto (the
-    list variant of the fast kernel), forced fast and forced generic; then one
+    """GCP R=20 (nq = 5: the pipelined pair loop with an odd quad count), n = 3
+    (one leaderless table), 5, 7 (two), 9 (two; the non-pipelined loop) and 11
+    (three: the second qtab plane on the Input side; the colocated lists of the
+    third table are the next test's), on auto (the list variant of the fast
+    kernel), forced fast and forced generic
+    (p75 over 11 members needs 4, the full list depth: still fast); then one
     sweep mixing MAX af1 with p95 and p99 af1: p99 over 20 clients is the
     maximum, so its records are the MAX records with T = 2 * max."""
     p, dp, _ = gcp
@@ -138,6 +141,24 @@ def test_gcp_full_sweep_vs_oracle(gcp, n):
         assert sw.kernel_path() == ("generic" if kernel == "generic" else "fast"), kernel
         assert tops == wantm, (n, kernel)
         assert [(2 * max_key(k)[0], max_key(k)[1], r) for k, r in tops[0]] == [pctl_key(k) + (r,) for k, r in tops[2]]
+
+
+def test_gcp_n11_colocated_third_table_vs_oracle(gcp):
+    """At n = 11 the third leaderless table is E's, and the only slot that reads
+    its colocated values is eC (5 + E), which objectives(11) has no room for
+    (MAXOBJ): p75 eC (needs 4 of the 11 members' values: the list variant's
+    second list of the qtab read-back) and MAX eC (its first entry), beside p95
+    e, on auto, forced fast and forced generic."""
+    p, dp, _ = gcp
+    srv = np.arange(p.R, dtype=np.uint32)
+    assert _lib.percentile_index(7500, 11) == (8, False)  # (the 8th smallest = the 4th largest)
+    objs = [(MEAN, AF1), (P(7500), 5 + E), (MAX, 5 + E), (P(9500), E)]
+    want = gcp_expected(gcp, 11, objs)
+    assert len({k for k, _ in want[1]}) > 1  # (the eC keys tell configs apart)
+    for kernel in KERNELS:
+        sw, tops = run(dp, srv, srv, 11, objs, kernel)
+        assert sw.kernel_path() == ("generic" if kernel == "generic" else "fast"), kernel
+        assert tops == want, kernel
 
 
 # --------------------------------------------------------------------- 2 ---
@@ -320,7 +341,7 @@ def test_sharded_equals_single(gcp):
 # --------------------------------------------------------------------- 8 ---
 def test_synthetic_r64_n7_window():
     """Synthetic R=64 n=7, one window of 65,536 colex ranks: 16 full client
-    quads (eight pipelined pairs and the flush), three leaderless tables.  Over
+    quads (eight pipelined pairs and the flush), two leaderless tables.  Over
     64 clients p95 needs 4 (the full list depth) and p99 needs 2."""
     p = Planet.synthetic(64)
     dp, o = DevicePlanet(p), O.OraclePlanet.of(p)

@@ -92,10 +92,12 @@ def gcp_expected(gcp, n):
 
 
 # ------------------------------------------------------------------ 1, 8 ---
-@pytest.mark.parametrize("n", [3, 5, 7, 9])
+@pytest.mark.parametrize("n", [3, 5, 7, 9, 11])
 def test_gcp_full_sweep_vs_oracle(gcp, n):
-    """GCP R=20 (nq = 5: the pipelined pair loop with an odd quad count), n = 3,
-    5, 7 (1..3 leaderless tables) and 9 (the non-pipelined loop), on auto (the
+    """GCP R=20 (nq = 5: the pipelined pair loop with an odd quad count), n = 3
+    (one leaderless table), 5, 7 (two), 9 (two; the non-pipelined loop) and 11
+    (three: the second qtab plane on the Input side, the smallest odd n that has
+    one; its colocated side is the next test's), on auto (the
     TAIL fast kernel), forced fast and forced generic.  Then, without the
     oracle: every reported record's key is rebuilt from eval_configs'
     per-client values of that rank."""
@@ -117,6 +119,22 @@ def test_gcp_full_sweep_vs_oracle(gcp, n):
             assert key == (int(x.sum()) if kind == MEAN else (int(x.max()) << 32) | int(x.sum())), (kind, slot, r)
             if kind == MAX:
                 assert max_key(key) == (int(x.max()), int(x.sum()))
+
+
+def test_gcp_n11_colocated_third_table_vs_oracle(gcp):
+    """At n = 11 the third leaderless table is E's, and the only slot that reads
+    its colocated values is eC (5 + E), which objectives(11) has no room for
+    (MAXOBJ): MAX eC (the Q phase's maximum of the third table), beside MAX e
+    and MAX af2C, on auto, forced fast and forced generic."""
+    p, dp, o = gcp
+    srv = np.arange(p.R, dtype=np.uint32)
+    objs = [(MEAN, AF1), (MAX, 5 + E), (MAX, E), (MAX, 5 + AF2)]
+    want = expected(o, srv, srv, 11, objs)
+    assert len({k for k, _ in want[1]}) > 1  # (the eC keys tell configs apart)
+    for kernel in KERNELS:
+        sw, tops = run(dp, srv, srv, 11, objs, kernel)
+        assert sw.kernel_path() == ("generic" if kernel == "generic" else "fast"), kernel
+        assert tops == want, kernel
 
 
 # --------------------------------------------------------------------- 2 ---
