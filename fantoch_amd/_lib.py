@@ -65,6 +65,8 @@ EXPORTS = [
     "bote_search_create", "bote_search_launch", "bote_search_result", "bote_search_bounds", "bote_search_destroy",
     "bote_eval_keys", "bote_sweep_create_keys", "bote_percentile_index",
     "bote_sweep_create_pinned", "bote_pinned_total", "bote_pinned_config",
+    "bote_batch_create", "bote_batch_launch", "bote_batch_result", "bote_batch_deferred", "bote_batch_path",
+    "bote_batch_last_kernel_ms", "bote_batch_plan", "bote_batch_destroy",
 ]
 KERNELS = {None: 0, "auto": 0, "generic": 1, "fast": 2, "group": 3}
 
@@ -187,6 +189,17 @@ def lib():
         L.bote_pinned_total.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]
         L.bote_pinned_config.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, _u32p, C.c_uint32, _u32p,
                                          C.POINTER(C.c_uint64)]
+    if hasattr(L, "bote_batch_create"):  # (the same)
+        L.bote_batch_create.argtypes = [_vp, _u32p, C.c_uint32, _u32p, C.c_uint32, C.c_uint32, _u32p, C.c_uint32,
+                                        C.c_uint32, C.c_uint32, C.POINTER(Objective), C.c_uint32, C.c_uint32,
+                                        C.POINTER(RankingParamsC), C.c_int, C.c_int, C.POINTER(_vp)]
+        L.bote_batch_launch.argtypes = [_vp, _vp]
+        L.bote_batch_result.argtypes = [_vp, _vp, C.POINTER(TopKRecord), _vp, _vp, _vp]
+        L.bote_batch_deferred.argtypes = [_vp, _vp, C.POINTER(C.c_uint64)]
+        L.bote_batch_path.argtypes = [_vp, C.POINTER(C.c_int)]
+        L.bote_batch_last_kernel_ms.argtypes = [_vp, C.POINTER(C.c_float)]
+        L.bote_batch_plan.argtypes = [_vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
+        L.bote_batch_destroy.argtypes = [_vp]
     if hasattr(L, "bote_percentile_index"):  # (absent from an older BOTE_LIB_PATH build loaded for A/B timing)
         L.bote_percentile_index.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_int)]
     _LIB = L

@@ -929,6 +929,97 @@ class Sweep:
         return [int(self.servers[p]) for p in pos]
 
 
+class PinnedBatch:
+    """Many pinned sweeps in one launch (bote_batch_*): `pinned_sets` are B sets of
+    the same size m, 1 <= m < n, of positions into `servers` (any order; sets may
+    be equal or overlap).  result() gives, per set, what Sweep(pinned=set) gives
+    over its whole rank space.  Base key set.  max_blocks caps the kernel's grid
+    (0: the device's)."""
+
+    def __init__(self, dp: DevicePlanet, servers: Sequence[int], clients: Sequence[int], n: int,
+                 pinned_sets: Sequence[Sequence[int]], objectives=DEFAULT_OBJECTIVES, K: int = 100,
+                 ranking: Optional[RankingParams] = DEFAULT_RANKING, digest: bool = False,
+                 kernel: Optional[str] = None, max_blocks: int = 0):
+        self.dp, self.n, self.K = dp, n, K
+        self.servers, self.clients = u32(servers), u32(clients)
+        sets = [u32(s) for s in pinned_sets]
+        if len({len(s) for s in sets}) > 1:
+            raise ValueError("the pinned sets of a batch have one size")
+        self.pinned_sets = np.ascontiguousarray(np.stack(sets)) if sets else np.zeros((0, 0), np.uint32)
+        self.objectives = list(objectives)
+        self.ranking, self.digest = ranking, bool(digest)
+        B, m = self.pinned_sets.shape
+        self.total = _lib.pinned_total(len(self.servers), n, m)  # per set
+        objs = (_lib.Objective * max(len(self.objectives), 1))(*[_lib.Objective(k, s) for k, s in self.objectives])
+        rp = C.byref(_lib.ranking_params_c(ranking)) if ranking is not None else None
+        self.h = None
+        h = C.c_void_p()
+        check(lib().bote_batch_create(dp.h, self.servers, len(self.servers), self.clients, len(self.clients), n,
+                                      self.pinned_sets.reshape(-1), B, m, max_blocks, objs, len(self.objectives), K, rp,
+                                      1 if digest else 0, _lib.KERNELS[kernel], C.byref(h)))
+        self.h = h
+
+    @classmethod
+    def from_records(cls, sweep: "Sweep", records: Sequence[Tuple[int, int]], n: int, **kw) -> "PinnedBatch":
+        """The batch over `sweep`'s planet and lists whose sets are the configs of `records`
+        ((key, rank) pairs of a result of `sweep`, a Sweep of a smaller config size): the
+        n-supersets of each, "extend the best of the last level".  Objectives, K, ranking
+        and digest default to the sweep's; `kw` overrides them or adds kernel, max_blocks."""
+        sets = [_lib.colex_unrank(int(r), sweep.n, len(sweep.servers)) for _, r in records]
+        for name in ("objectives", "K", "ranking", "digest"):
+            kw.setdefault(name, getattr(sweep, name))
+        return cls(sweep.dp, sweep.servers, sweep.clients, n, sets, **kw)
+
+    def __del__(self):
+        try:
+            if self.h:
+                lib().bote_batch_destroy(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+    def launch(self, stream: Optional[int] = None):
+        check(lib().bote_batch_launch(self.h, C.c_void_p(stream) if stream else None))
+
+    def result(self, stream: Optional[int] = None) -> List[SweepResult]:
+        B, no, K = len(self.pinned_sets), len(self.objectives), self.K
+        recs = np.zeros((B, max(no, 1), K, 2), np.uint64)
+        cnt = np.zeros((B, max(no, 1)), np.uint32)
+        valid, digest = np.zeros(B, np.uint64), np.zeros(B, np.uint64)
+        check(lib().bote_batch_result(self.h, C.c_void_p(stream) if stream else None,
+                                      recs.ctypes.data_as(C.POINTER(_lib.TopKRecord)), ptr(cnt), ptr(valid), ptr(digest)))
+        if no:
+            recs = recs.reshape(B, no, K, 2)
+        return [SweepResult([list(map(tuple, recs[b, o, :cnt[b, o]].tolist())) for o in range(no)],
+                            int(valid[b]), int(digest[b])) for b in range(B)]
+
+    def deferred(self, stream: Optional[int] = None) -> int:
+        """Configs the last launch deferred to the exact generic kernel, over all sets."""
+        v = C.c_uint64()
+        check(lib().bote_batch_deferred(self.h, C.c_void_p(stream) if stream else None, C.byref(v)))
+        return v.value
+
+    def kernel_path(self) -> str:
+        v = C.c_int()
+        check(lib().bote_batch_path(self.h, C.byref(v)))
+        return ("generic", "fast")[v.value]
+
+    def kernel_ms(self) -> float:
+        v = C.c_float()
+        check(lib().bote_batch_last_kernel_ms(self.h, C.byref(v)))
+        return v.value
+
+    def plan(self) -> Tuple[int, int, int]:
+        """(slices per set, units, grid) of the batch kernel."""
+        s, u, g = C.c_uint32(), C.c_uint64(), C.c_uint32()
+        check(lib().bote_batch_plan(self.h, C.byref(s), C.byref(u), C.byref(g)))
+        return s.value, u.value, g.value
+
+    def config_of(self, rank: int) -> List[int]:
+        pos = _lib.colex_unrank(rank, self.n, len(self.servers))
+        return [int(self.servers[p]) for p in pos]
+
+
 class MultiDeviceSearch:
     """bote_search_*: the sweep sharded over `planets` (one per shard; the same
     device may appear more than once), merged on planets[0]'s device, without

@@ -20,7 +20,7 @@ main.rs:31-60).  Subcommands expose them, and the sweep the hot path serves:
   python -m fantoch_amd sweep (--synthetic R [--seed S] | --lat-dir D) --n N [--K 100]
                         [--objectives default|config5|mean:af1,cov:af1,max:af1,p95:af1,p99.9:e,mdtm:af1,score,...]
                         [--keys base|tempo-all-leaders] [--gpus G] [--rank-begin B --rank-end E]
-                        [--pinned a,b | --pinned 3,9]
+                        [--pinned a,b | --pinned 3,9 | --pinned-sets "a,b;c,d"]
 """
 from __future__ import annotations
 
@@ -178,7 +178,17 @@ def _pinned(spec: Optional[str], names: Sequence[str]) -> Optional[List[int]]:
     return out
 
 
-def sweep(args, out=sys.stdout) -> dict:
+def _pinned_sets(spec: Optional[str], names: Sequence[str]) -> Optional[List[List[int]]]:
+    """--pinned-sets: ';'-separated --pinned lists, all of one size."""
+    if not spec:
+        return None
+    sets = [_pinned(part, names) for part in spec.split(";")]
+    if any(s is None for s in sets) or len({len(s) for s in sets}) != 1:
+        raise ValueError("--pinned-sets: every set needs the same number of members, at least one")
+    return sets
+
+
+def sweep(args, out=sys.stdout):
     """The exhaustive sweep of every n-subset (search.rs:199-319 + the ranking's
     compute_score, search.rs:421-472) streamed through the device top-K, sharded
     over --gpus devices (bote_search_*), as one JSON object: per objective the
@@ -186,7 +196,7 @@ def sweep(args, out=sys.stdout) -> dict:
     import numpy as np
 
     from . import _lib
-    from .bote import DEFAULT_RANKING, DevicePlanet, MultiDeviceSearch, Sweep, max_key, mdtm_key, pctl_key
+    from .bote import DEFAULT_RANKING, DevicePlanet, MultiDeviceSearch, PinnedBatch, Sweep, max_key, mdtm_key, pctl_key
 
     planet = _planet(args)
     srv = np.arange(planet.R, dtype=np.uint32)
@@ -195,11 +205,23 @@ def sweep(args, out=sys.stdout) -> dict:
     pinned = _pinned(getattr(args, "pinned", None), planet.names)
     if pinned is not None and (args.gpus > 1 or keys != _lib.KEYS_BASE):
         raise ValueError("--pinned sweeps run on one device with the base key set")
+    sets = _pinned_sets(getattr(args, "pinned_sets", None), planet.names)
+    if sets is not None:
+        if pinned is not None:
+            raise ValueError("--pinned-sets and --pinned exclude each other")
+        if args.gpus > 1 or keys != _lib.KEYS_BASE or args.rank_begin is not None or args.rank_end is not None:
+            raise ValueError("--pinned-sets sweeps every set's whole rank space on one device with the base key set")
     # (--rank-begin / --rank-end of a pinned sweep are pinned ranks)
     total = _lib.binomial(planet.R, args.n) if pinned is None else _lib.pinned_total(planet.R, args.n, len(pinned))
     rb = args.rank_begin or 0
     re = total if args.rank_end is None else args.rank_end
-    if args.gpus > 1:
+    if sets is not None:
+        total = re = _lib.pinned_total(planet.R, args.n, len(sets[0]))
+        batch = PinnedBatch(DevicePlanet(planet, args.device), srv, srv, args.n, sets, objs, K=args.K,
+                            ranking=DEFAULT_RANKING, digest=True)
+        batch.launch()
+        results = batch.result()
+    elif args.gpus > 1:
         dps = [DevicePlanet(planet, d) for d in range(args.gpus)]
         h = MultiDeviceSearch(dps, srv, srv, args.n, objectives=objs, K=args.K, ranking=DEFAULT_RANKING,
                               rank_begin=rb, rank_end=re, keys=keys)
@@ -228,15 +250,20 @@ def sweep(args, out=sys.stdout) -> dict:
             rec["mdtm"], rec["sum"] = 2 * h / count ** 2, total
         return rec
 
-    doc = {"regions": planet.R, "n": args.n, "rank_begin": rb, "rank_end": re, "configs": re - rb,
-           "keys": args.keys, "gpus": args.gpus, "valid": res.valid, "digest": str(res.digest),
-           "objectives": [{"objective": _objective_name(k) + ("" if k == _lib.OBJ_SCORE else ":" + _lib.SLOT_NAMES_X[s]),
-                           "top": [record(k, s, key, rank) for key, rank in res.tops[o][:args.show]]}
-                          for o, (k, s) in enumerate(objs)]}
-    if pinned is not None:
-        doc["pinned"] = pinned
-    print(json.dumps(doc, indent=None if args.compact else 1), file=out)
-    return doc
+    def block(res, pinned):
+        doc = {"regions": planet.R, "n": args.n, "rank_begin": rb, "rank_end": re, "configs": re - rb,
+               "keys": args.keys, "gpus": args.gpus, "valid": res.valid, "digest": str(res.digest),
+               "objectives": [{"objective": _objective_name(k) + ("" if k == _lib.OBJ_SCORE else ":" + _lib.SLOT_NAMES_X[s]),
+                               "top": [record(k, s, key, rank) for key, rank in res.tops[o][:args.show]]}
+                              for o, (k, s) in enumerate(objs)]}
+        if pinned is not None:
+            doc["pinned"] = pinned
+        print(json.dumps(doc, indent=None if args.compact else 1), file=out)
+        return doc
+
+    if sets is not None:  # one block per set, each as --pinned prints that set
+        return [block(r, s) for r, s in zip(results, sets)]
+    return block(res, pinned)
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -287,6 +314,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--rank-end", type=int, default=None)
     p.add_argument("--pinned", default=None,
                    help="region names or positions every swept config contains (rank flags are then pinned ranks)")
+    p.add_argument("--pinned-sets", default=None,
+                   help="';'-separated --pinned lists of one size: one launch sweeps every set, one block per set")
     p.add_argument("--compact", action="store_true")
     return ap
 

@@ -720,6 +720,37 @@ Status check_pinned_args(uint32_t ns, uint32_t n, const uint32_t* pinned, uint32
   return OK;
 }
 
+Status check_batch_args(uint32_t ns, uint32_t n, const uint32_t* pinned, uint32_t n_sets, uint32_t m, uint32_t keys) {
+  if (n_sets == 0 || n_sets > BATCH_MAX_SETS)
+    return fail(BOTE_E_ARG, "a batch takes 1 to " + std::to_string(BATCH_MAX_SETS) + " pinned sets");
+  if (!pinned || m == 0 || m >= n) return fail(BOTE_E_ARG, "pinned sets must hold 1 to n - 1 positions");
+  for (uint32_t b = 0; b < n_sets; ++b) {
+    const uint32_t* set = pinned + (size_t)b * m;
+    for (uint32_t i = 0; i < m; ++i)
+      if (set[i] >= ns) return fail(BOTE_E_ARG, "pinned set " + std::to_string(b) + ": position out of range");
+    for (uint32_t i = 0; i < m; ++i)
+      for (uint32_t j = 0; j < i; ++j)
+        if (set[i] == set[j]) return fail(BOTE_E_ARG, "pinned set " + std::to_string(b) + ": duplicate position");
+  }
+  if (keys) return fail(BOTE_E_ARG, "batched pinned sweeps compute the base key set");
+  return OK;
+}
+
+BatchPlan batch_plan(uint32_t ns, uint32_t n, uint32_t m, uint32_t n_sets, uint32_t grid_cap) {
+  BatchPlan p;
+  const uint64_t total = pinned_total(ns, n, m);
+  if (!total || !n_sets) return p;
+  p.total = total;
+  const uint64_t passes = (total + BATCH_PASS - 1) / BATCH_PASS;
+  const uint64_t fill = grid_cap ? (grid_cap + (uint64_t)n_sets - 1) / n_sets : BATCH_MAX_SLICES;
+  p.slices = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>({passes, fill, BATCH_MAX_SLICES}));
+  p.slice_len = (total + p.slices - 1) / p.slices;
+  for (uint32_t s = 0; s <= p.slices; ++s) p.bounds.push_back(std::min<uint64_t>((uint64_t)s * p.slice_len, total));
+  p.units = (uint64_t)n_sets * p.slices;
+  p.runlen = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(32, (p.slice_len + BATCH_LANES - 1) / BATCH_LANES));
+  return p;
+}
+
 Status check_rank_span_total(uint64_t total, uint64_t rank_begin, uint64_t rank_end) {
   if (rank_begin > rank_end || rank_end > total) return fail(BOTE_E_ARG, "rank range out of bounds");
   return OK;

@@ -268,6 +268,30 @@ Status check_sweep_args(uint32_t R, const uint32_t* servers, uint32_t ns, const 
 // entry takes none: the internal path only).
 Status check_pinned_args(uint32_t ns, uint32_t n, const uint32_t* pinned, uint32_t n_pinned, int kernel,
                          uint32_t keys);
+// bote_batch_create, after check_sweep_args; check_pinned_args on set 0 follows
+// it (a forced group kernel, with the pinned sweep's text).  In order: the set
+// count (1 .. BATCH_MAX_SETS), a null list or m outside 1 .. n - 1, then per
+// set, lowest index first, a position >= ns and a repeated position, each
+// naming the set; then the extended key set.
+constexpr uint32_t BATCH_MAX_SETS = BOTE_BATCH_MAX_SETS;
+Status check_batch_args(uint32_t ns, uint32_t n, const uint32_t* pinned, uint32_t n_sets, uint32_t m, uint32_t keys);
+// The unit plan of a batch (DESIGN.md §4 "Batched pinned sweeps"): every set's
+// C(ns - m, n - m) pinned ranks are cut into the same `slices` slices, slice s
+// being [bounds[s], bounds[s + 1]), and a unit is (set, slice): units = B *
+// slices.  One slice when a set fits one pass of a workgroup (BATCH_PASS
+// configs); otherwise as many as fill the grid (`grid_cap` workgroups; 0: no
+// cap, as many as there are), at most BATCH_MAX_SLICES, so that the slices'
+// lists and the set's fix-up list are one 8-way merge group.  `runlen`: the
+// consecutive ranks of a lane job.  slices == 0: bad sizes.
+constexpr uint32_t BATCH_MAX_SLICES = 7, BATCH_PASS = 8192, BATCH_LANES = 256;
+struct BatchPlan {
+  uint32_t slices = 0;
+  uint64_t total = 0, slice_len = 0;
+  std::vector<uint64_t> bounds;  // slices + 1
+  uint64_t units = 0;
+  uint32_t runlen = 0;
+};
+BatchPlan batch_plan(uint32_t ns, uint32_t n, uint32_t m, uint32_t n_sets, uint32_t grid_cap);
 // rank_begin <= rank_end <= `total` (a pinned sweep's pinned_total).
 Status check_rank_span_total(uint64_t total, uint64_t rank_begin, uint64_t rank_end);
 // bote_evolving_chains' six levels (n = 3, 5, .., 13): arrays present where a

@@ -198,6 +198,28 @@ struct PinArgs {
   uint32_t pin_n;      // m
   uint32_t pin[MAXN];  // the pinned positions, ascending; 0 from pin_n on
 };
+// A batch of pinned sweeps (DESIGN.md §4 "Batched pinned sweeps"): n_sets
+// pinned sets of one size, each swept over its whole pinned-rank space in one
+// launch of the fast kernel's batch variant.  The work is cut into units
+// (set b, slice s), unit u = b * slices + s, slice s being the pinned ranks
+// [s * slice_len, min((s + 1) * slice_len, ptotal)); a workgroup walks units
+// blockIdx.x, += gridDim.x.  Unit u's lists go to list slot b * BATCH_SET_LISTS
+// + s of out_top, set b's valid count and digest to out_counters[2 b .. 2 b + 1].
+// Deferred configs are only counted (queue_count): a batch that deferred any is
+// recomputed set by set on the generic kernel when its result is fetched.
+constexpr uint32_t BATCH_SET_LISTS = G_MERGE_LISTS;         // list slots per set: one merge group
+constexpr uint32_t BATCH_MAX_SLICES = BATCH_SET_LISTS - 1;  // (one slot is kept for a per-set fix-up list)
+struct BatchArgs {
+  const PinArgs* sets;  // [n_sets], positions ascending
+  uint32_t n_sets, slices;
+  uint64_t slice_len, ptotal;
+  uint32_t runlen;  // consecutive pinned ranks per lane job of a unit
+};
+// the fast kernel's member stage (bote_sweep.hip Members).  Plain ints, not
+// enumerators of an unnamed enum: where one appears in a kernel's signature the
+// host and the device pass number the enum differently, the mangled names
+// differ and the runtime does not find the kernel.
+constexpr int PIN_NONE = 0, PIN_ONE = 1, PIN_BATCH = 2;
 #ifdef BOTE_DEBUG
 // bit `code` of *dbg_flag when `cond` fails (codes: DESIGN.md §5, debug build)
 #define GASSERT(a, cond, code)                                                    \
@@ -236,11 +258,14 @@ struct PinArgs {
 // MDTM objective beside a MAX or percentile one runs the generic kernel
 enum { FAST_PLAIN = 0, FAST_MAX = 1, FAST_LIST = 2, FAST_MDTM = 3 };
 size_t fast_smem_bytes(const FastArgs& a, uint32_t n, int tail);
-// (pin: the pinned variant, FAST_PLAIN only: SCORE, MEAN and COV objectives)
-int fast_occupancy(uint32_t n, int tail, bool pin, size_t shm);
+// (pin: PIN_*; the pinned and the batch variant are FAST_PLAIN only: SCORE, MEAN and COV objectives)
+int fast_occupancy(uint32_t n, int tail, int pin, size_t shm);
 // (e0, e1: events carried by the dispatch itself, bote_launch.hpp, for a timed launch)
 hipError_t launch_fast(const FastArgs& a, uint32_t n, int tail, const PinArgs* pin, uint32_t grid, size_t shm,
                        hipStream_t st, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
+// the batch variant (FAST_PLAIN) over the units of `b`; a.rb, a.re and a.runlen are not read
+hipError_t launch_fast_batch(const FastArgs& a, uint32_t n, const BatchArgs& b, uint32_t grid, size_t shm,
+                             hipStream_t st, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
 size_t group_smem_bytes(const FastArgs& a, uint32_t n);
 bool group_uses_lines(uint32_t n);  // n <= 7: client lines (FastArgs::gslots) and register lookups
 // the extended key set's group kernels target BOTE_GROUP_WAVES_XK waves per

@@ -29,6 +29,11 @@ struct PinFastArgs : FastArgs {
 struct PinEvalArgs : EvalArgs {
   PinArgs pz;
 };
+// A batch of pinned sets (BatchArgs, bote_kernels.hpp): the fast kernel's
+// batch variant reads a unit's set from the device table bz.sets.
+struct BatchFastArgs : FastArgs {
+  BatchArgs bz;
+};
 
 // pinned rank -> q (binom: the (ns + 1) x (N + 1) table, which holds every
 // C(x, k) with x <= ns - m, k <= F at the same stride)

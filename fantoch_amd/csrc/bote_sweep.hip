@@ -334,35 +334,39 @@ __device__ __forceinline__ void position_sums(const FastArgs& a, const FastSmem&
 // them over the free indices q and re-merges the members per step.  The full
 // colex rank is computed with the members, always: the digest, a record
 // offered to the top-K and a deferred config's queue entry carry it, and
-// everything after p[N] is the code of the unpinned kernel.
-template <int N, bool PIN>
+// everything after p[N] is the code of the unpinned kernel.  PIN is a mode
+// (PIN_*, bote_kernels.hpp): PIN_ONE takes the pinned set `z` from the kernarg,
+// PIN_BATCH the set of the unit at hand, loaded from the batch's device table
+// (the kernel below); both walk it the same way.
+template <int N, int PIN>
 struct Members {
-  using Args = std::conditional_t<PIN, PinFastArgs, FastArgs>;
+  using Args = std::conditional_t<PIN == PIN_BATCH, BatchFastArgs, std::conditional_t<PIN == PIN_ONE, PinFastArgs, FastArgs>>;
   uint32_t p[N];
   [[maybe_unused]] uint32_t q[PIN ? N : 1];  // PIN: the free indices (one unused word otherwise)
 
-  __device__ __forceinline__ void start(const uint64_t* binom, const Args& a, bool jobok, uint64_t rank) {
+  __device__ __forceinline__ void start(const uint64_t* binom, uint32_t ns, const PinArgs& z, bool jobok,
+                                        uint64_t rank) {
 #pragma unroll
     for (int j = 0; j < N; ++j) p[j] = j;
-    if constexpr (PIN) {
+    if constexpr (PIN != PIN_NONE) {
 #pragma unroll
       for (int j = 0; j < N; ++j) q[j] = 0;
-      if (jobok) pin_unrank<N>(binom, a.ns, a.pz, rank, q);
+      if (jobok) pin_unrank<N>(binom, ns, z, rank, q);
     } else {
-      if (jobok) colex_unrank<N>(binom, a.ns, rank, p);
+      if (jobok) colex_unrank<N>(binom, ns, rank, p);
     }
   }
   // the members of the config at hand; `frank` comes in as the rank and leaves as the full colex rank
-  __device__ __forceinline__ void config(const uint64_t* binom, const Args& a, bool have, uint64_t& frank) {
-    if constexpr (PIN) {
-      if (have) pin_members<N>(binom, a.pz, q, p, frank);
+  __device__ __forceinline__ void config(const uint64_t* binom, const PinArgs& z, bool have, uint64_t& frank) {
+    if constexpr (PIN != PIN_NONE) {
+      if (have) pin_members<N>(binom, z, q, p, frank);
     }
   }
-  __device__ __forceinline__ void next(const Args& a, bool live) {
-    if constexpr (PIN) {
-      if (live) pin_next<N>(a.ns, a.pz, q);
+  __device__ __forceinline__ void next(uint32_t ns, const PinArgs& z, bool live) {
+    if constexpr (PIN != PIN_NONE) {
+      if (live) pin_next<N>(ns, z, q);
     } else {
-      if (live) colex_next<N>(a.ns, p);
+      if (live) colex_next<N>(ns, p);
     }
   }
 };
@@ -512,11 +516,15 @@ __device__ __forceinline__ void colocated(const unsigned char* B, const Leader& 
 
 // ---------------------------------------------------------- the kernel ----
 // The stages above in order; what a variant adds is in its carrier (Tail) and
-// in the member stage (Members).
-template <int N, int TAIL, bool PIN = false>
-__global__ void __launch_bounds__(FAST_BD, 4) sweep_fast_kernel(std::conditional_t<PIN, PinFastArgs, FastArgs> a) {
+// in the member stage (Members).  PIN_BATCH (FAST_PLAIN): the workgroup stages
+// the planet once, then walks the batch's units blockIdx.x, += gridDim.x
+// (BatchArgs): per unit its own rank range and pinned set, a fresh block top-K
+// and fresh valid and digest sums, the unit's list slot and the set's counters.
+template <int N, int TAIL, int PIN = PIN_NONE>
+__global__ void __launch_bounds__(FAST_BD, 4) sweep_fast_kernel(typename Members<N, PIN>::Args a) {
   using TL = Tail<N, TAIL>;
-  static_assert(!PIN || TL::plain, "the pinned variant computes SCORE, MEAN and COV objectives");
+  static_assert(PIN == PIN_NONE || TL::plain, "the pinned variants compute SCORE, MEAN and COV objectives");
+  constexpr bool BATCH = PIN == PIN_BATCH;
   constexpr int NL = TL::NL;
   extern __shared__ __align__(16) unsigned char smem[];
   const FastSmem s = fast_smem(fast_layout(a, N, NL <= 2 ? 1 : 2, TAIL), smem);
@@ -530,84 +538,129 @@ __global__ void __launch_bounds__(FAST_BD, 4) sweep_fast_kernel(std::conditional
   const uint32_t rstride = a.rq_stride * 8;
   const uint32_t nc = a.nc;
   const uint32_t qlane = s.qtab + tid * 4;
-  const uint64_t total = a.re - a.rb;
-  const uint64_t runlen = a.runlen;
-  const uint64_t njobs = (total + runlen - 1) / runlen;
-  const uint64_t G = (uint64_t)gridDim.x * FAST_BD;
-  const uint64_t outer = (njobs + G - 1) / G;
   const double pnc1 = a.p_fmean * (double)nc, pnc2 = a.p_emean * (double)nc;
-  uint64_t valid_cnt = 0, digest = 0;
   const uint32_t tail_slots = TL::slots(a);
-
-  for (uint64_t it = 0; it < outer; ++it) {
-    const uint64_t job = it * G + (uint64_t)blockIdx.x * FAST_BD + tid;
-    const bool jobok = job < njobs;
-    uint64_t rank = a.rb + job * runlen;
-    Members<N, PIN> mb;
-    mb.start(s.binom, a, jobok, rank);
-    for (uint64_t tt = 0; tt < runlen; ++tt) {
-      bool have = jobok && rank < a.re;
-      uint64_t frank = rank;  // the config's full colex rank
-      mb.config(s.binom, a, have, frank);
-      uint64_t key[MAXOBJ];
-      bool ok[MAXOBJ];
-#pragma unroll
-      for (int o = 0; o < MAXOBJ; ++o) {
-        key[o] = 0;
-        ok[o] = false;
+  // the rank range at hand and the lane jobs' spacing: the launch's, or the unit's
+  uint64_t rb = a.rb, re = a.re, runlen = a.runlen;
+  uint64_t G = (uint64_t)gridDim.x * FAST_BD, first = (uint64_t)blockIdx.x * FAST_BD + tid;
+  [[maybe_unused]] uint32_t unit = blockIdx.x, set = 0;  // (block-uniform)
+  [[maybe_unused]] PinArgs zb{};                         // BATCH: the unit's pinned set
+  const PinArgs& pz = [&]() -> const PinArgs& {
+    if constexpr (PIN == PIN_ONE) return a.pz;
+    else return zb;
+  }();
+  Rec* dst = a.out_top + (size_t)blockIdx.x * a.n_obj * KP;
+  unsigned long long* counters = a.out_counters;
+  if constexpr (BATCH) {
+    if (unit >= a.bz.n_sets * a.bz.slices) return;  // (the launcher's grid is at most the units)
+    G = FAST_BD;
+    first = tid;
+    runlen = a.bz.runlen;
+  }
+  bool more = false;  // BATCH: another unit for this workgroup
+  do {
+    if constexpr (BATCH) {
+      set = unit / a.bz.slices;
+      const uint32_t sl = unit - set * a.bz.slices;
+      rb = min((uint64_t)sl * a.bz.slice_len, a.bz.ptotal);
+      re = min(rb + a.bz.slice_len, a.bz.ptotal);
+      zb = a.bz.sets[set];  // (uniform loads)
+      dst = a.out_top + ((size_t)set * BATCH_SET_LISTS + sl) * a.n_obj * KP;
+      counters = a.out_counters + 2 * (size_t)set;
+      if (unit != blockIdx.x) {  // the last unit's list is out: a fresh top-K
+        __syncthreads();
+        topk_init(s.tk, a.n_obj);
+        __syncthreads();
       }
-      if (have) {
-        // ---- members (positions ascending == names ascending)
-        uint32_t colT[N], colR[N], rowq[N];
+    }
+    const uint64_t total = re - rb;
+    const uint64_t njobs = (total + runlen - 1) / runlen;
+    const uint64_t outer = (njobs + G - 1) / G;
+    uint64_t valid_cnt = 0, digest = 0;
+
+    for (uint64_t it = 0; it < outer; ++it) {
+      const uint64_t job = it * G + first;
+      const bool jobok = job < njobs;
+      uint64_t rank = rb + job * runlen;
+      Members<N, PIN> mb;
+      mb.start(s.binom, a.ns, pz, jobok, rank);
+      for (uint64_t tt = 0; tt < runlen; ++tt) {
+        bool have = jobok && rank < re;
+        uint64_t frank = rank;  // the config's full colex rank
+        mb.config(s.binom, pz, have, frank);
+        uint64_t key[MAXOBJ];
+        bool ok[MAXOBJ];
 #pragma unroll
-        for (int j = 0; j < N; ++j) {
-          const uint32_t r = a.srv_identity ? mb.p[j] : s.srv[mb.p[j]];
-          colT[j] = r * cstride;
-          colR[j] = s.rqt + r * rstride;
-          rowq[j] = (r >> 2) * 8 + (r & 3) * 2;
+        for (int o = 0; o < MAXOBJ; ++o) {
+          key[o] = 0;
+          ok[o] = false;
         }
-        TL tl(tail_slots);
-        uint32_t Q2[N], Q3[N], cS1[NL], cS2[NL];
-        q_phase<N>(a, smem, colR, rowq, qlane, Q2, Q3, cS1, cS2, tl);
-        Leader ld;
-        if (!fpaxos_leader<N>(s, mb.p, nc, Q2, Q3, colR, ld)) {  // to the exact generic kernel (bote_sweep_launch)
-          defer_rank(a, frank);
-          have = false;
-        }
+        // a deferred config goes to the exact generic kernel (bote_sweep_launch; BATCH: the
+        // count alone matters, a batch that deferred any config is recomputed on that kernel)
+        auto defer = [&]() { defer_rank(a, frank); };
         if (have) {
-          Mom mom[NSLOT];
-          input_leaderless<N>(B, s.cqt, nc, colT, qlane, mom, tl, a, key, ok);
-          input_fpaxos(s, ld, nc, mom, tl, a, key, ok);
-          colocated<N>(B, ld, rowq, qlane, cS1, cS2, mom, tl, a, key, ok);
-          tl.build_keys(ld.lq2, ld.lq3, TailKeys{a, mom, key, ok});
-          if (!finish_config<N, TAIL>(a, mom, s.vcol[ld.lp], ld.bi, frank, s.tk.thr, pnc1, pnc2, valid_cnt, digest, key,
-                                      ok)) {
-            defer_rank(a, frank);
+          // ---- members (positions ascending == names ascending)
+          uint32_t colT[N], colR[N], rowq[N];
+#pragma unroll
+          for (int j = 0; j < N; ++j) {
+            const uint32_t r = a.srv_identity ? mb.p[j] : s.srv[mb.p[j]];
+            colT[j] = r * cstride;
+            colR[j] = s.rqt + r * rstride;
+            rowq[j] = (r >> 2) * 8 + (r & 3) * 2;
+          }
+          TL tl(tail_slots);
+          uint32_t Q2[N], Q3[N], cS1[NL], cS2[NL];
+          q_phase<N>(a, smem, colR, rowq, qlane, Q2, Q3, cS1, cS2, tl);
+          Leader ld;
+          if (!fpaxos_leader<N>(s, mb.p, nc, Q2, Q3, colR, ld)) {
+            defer();
             have = false;
-            TL::withdraw(ok);
+          }
+          if (have) {
+            Mom mom[NSLOT];
+            input_leaderless<N>(B, s.cqt, nc, colT, qlane, mom, tl, a, key, ok);
+            input_fpaxos(s, ld, nc, mom, tl, a, key, ok);
+            colocated<N>(B, ld, rowq, qlane, cS1, cS2, mom, tl, a, key, ok);
+            tl.build_keys(ld.lq2, ld.lq3, TailKeys{a, mom, key, ok});
+            if (!finish_config<N, TAIL>(a, mom, s.vcol[ld.lp], ld.bi, frank, s.tk.thr, pnc1, pnc2, valid_cnt, digest,
+                                        key, ok)) {
+              defer();
+              have = false;
+              TL::withdraw(ok);
+            }
           }
         }
+        if (!ABLATE(a, 4)) topk_step(s.tk, a.n_obj, a.K, key, ok, frank);
+        mb.next(a.ns, pz, jobok && rank < re);
+        ++rank;
       }
-      if (!ABLATE(a, 4)) topk_step(s.tk, a.n_obj, a.K, key, ok, frank);
-      mb.next(a, jobok && rank < a.re);
-      ++rank;
     }
-  }
-  if (valid_cnt) atomicAdd(&a.out_counters[0], (unsigned long long)valid_cnt);
-  if (digest) atomicAdd(&a.out_counters[1], (unsigned long long)digest);
-  __syncthreads();
-  Rec* dst = a.out_top + (size_t)blockIdx.x * a.n_obj * KP;
-  for (uint32_t i = tid; i < (uint32_t)a.n_obj * KP; i += FAST_BD) dst[i] = s.tk.top[i];
+    if constexpr (BATCH) {  // one add per wave: the sets' counters take a unit's adds at once
+#pragma unroll
+      for (int d = 32; d >= 1; d >>= 1) {
+        valid_cnt += (uint64_t)__shfl_xor((long long)valid_cnt, d);
+        digest += (uint64_t)__shfl_xor((long long)digest, d);
+      }
+      if (tid & 63) valid_cnt = digest = 0;
+    }
+    if (valid_cnt) atomicAdd(&counters[0], (unsigned long long)valid_cnt);
+    if (digest) atomicAdd(&counters[1], (unsigned long long)digest);
+    __syncthreads();
+    for (uint32_t i = tid; i < (uint32_t)a.n_obj * KP; i += FAST_BD) dst[i] = s.tk.top[i];
+    if constexpr (BATCH) more = (unit += gridDim.x) < a.bz.n_sets * a.bz.slices;
+  } while (more);
 }
 
 // ------------------------------------------------------------- launcher ---
-// the kernel for config size n (null: unsupported; the pinned variant is
-// FAST_PLAIN only), for the occupancy query and the launch alike
-static const void* fast_fn(uint32_t n, int tail, bool pin) {
+// the kernel for config size n (null: unsupported; the pinned and the batch
+// variant, pin = PIN_*, are FAST_PLAIN only), for the occupancy query and the
+// launch alike
+static const void* fast_fn(uint32_t n, int tail, int pin) {
   switch (n) {
 #define FN_CASE(NN)                                                                  \
   case NN:                                                                           \
-    if (pin) return tail == FAST_PLAIN ? (const void*)sweep_fast_kernel<NN, FAST_PLAIN, true> : nullptr; \
+    if (pin == PIN_BATCH) return tail == FAST_PLAIN ? (const void*)sweep_fast_kernel<NN, FAST_PLAIN, PIN_BATCH> : nullptr; \
+    if (pin == PIN_ONE) return tail == FAST_PLAIN ? (const void*)sweep_fast_kernel<NN, FAST_PLAIN, PIN_ONE> : nullptr; \
     return tail == FAST_MDTM   ? (const void*)sweep_fast_kernel<NN, FAST_MDTM>       \
            : tail == FAST_LIST ? (const void*)sweep_fast_kernel<NN, FAST_LIST>       \
            : tail == FAST_MAX  ? (const void*)sweep_fast_kernel<NN, FAST_MAX>        \
@@ -619,20 +672,32 @@ static const void* fast_fn(uint32_t n, int tail, bool pin) {
   }
 }
 
-int fast_occupancy(uint32_t n, int tail, bool pin, size_t shm) {
+int fast_occupancy(uint32_t n, int tail, int pin, size_t shm) {
   const void* k = fast_fn(n, tail, pin);
   return k ? kernel_occupancy(k, FAST_BD, shm, 1) : 0;
 }
 
 hipError_t launch_fast(const FastArgs& a, uint32_t n, int tail, const PinArgs* pin, uint32_t grid, size_t shm,
                        hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
-  const void* k = fast_fn(n, tail, pin != nullptr);
+  const void* k = fast_fn(n, tail, pin ? PIN_ONE : PIN_NONE);
   if (!k) return hipErrorInvalidValue;
   if (!pin) return launch_kernel(k, a, grid, FAST_BD, shm, st, e0, e1);
   PinFastArgs pa{};
   static_cast<FastArgs&>(pa) = a;
   pa.pz = *pin;
   return launch_kernel(k, pa, grid, FAST_BD, shm, st, e0, e1);
+}
+
+hipError_t launch_fast_batch(const FastArgs& a, uint32_t n, const BatchArgs& b, uint32_t grid, size_t shm,
+                             hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
+  const void* k = fast_fn(n, FAST_PLAIN, PIN_BATCH);
+  const uint64_t units = (uint64_t)b.n_sets * b.slices;
+  if (!k || !b.sets || !units || b.slices > BATCH_MAX_SLICES || !b.runlen || grid > units)
+    return hipErrorInvalidValue;
+  BatchFastArgs ba{};
+  static_cast<FastArgs&>(ba) = a;
+  ba.bz = b;
+  return launch_kernel(k, ba, grid, FAST_BD, shm, st, e0, e1);
 }
 
 }  // namespace bote

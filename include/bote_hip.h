@@ -38,6 +38,7 @@ extern "C" {
 #define BOTE_MAX_OBJECTIVES 8
 #define BOTE_MAX_LATENCY 16383
 #define BOTE_MAX_CLIENTS 4096
+#define BOTE_BATCH_MAX_SETS 1024 /* pinned sets per bote_batch */
 
 /* --------------------------------------------------------------- enums    */
 /* fantoch_bote/src/protocol.rs:5-9 (+ Tempo, fantoch/src/config.rs:317-329) */
@@ -392,6 +393,52 @@ int bote_sweep_grid(const bote_sweep* s, uint32_t* out_grid, uint32_t* out_block
 /* A sweep may be destroyed after its planet (it keeps the planet's device
  * itself); every other entry needs the planet alive. */
 int bote_sweep_destroy(bote_sweep* s);
+
+/* --------------------------------------------- batched pinned sweeps --- */
+/* One handle for n_sets pinned sets of the same size n_pinned (1 <= n_pinned <
+ * n, 1 <= n_sets <= BOTE_BATCH_MAX_SETS): pinned[b * n_pinned ..] are set b's
+ * distinct positions into `servers`, in any order; sets may be equal or
+ * overlap.  One launch sweeps the supersets of every set, and the result of
+ * set b is exactly what bote_sweep_create_pinned with set b and the same
+ * arguments gives over its whole rank space [0, bote_pinned_total(ns, n,
+ * n_pinned)): lists ordered by (key, full colex rank), counts, valid count
+ * and digest.  Sets do not interact: a superset of two sets is evaluated for
+ * both.  The streaming counterpart of the reference's super_configs step
+ * (search.rs:97-178): rank the extensions of the best configs of the last
+ * level.  Base key set.
+ * Routing as for pinned sweeps: AUTO or forced fast on an eligible planet with
+ * only SCORE, MEAN and COV objectives runs the fast kernel's batch variant
+ * (one launch for all sets, then one merge launch; bote_batch_path gives 1); AUTO with a MAX, percentile
+ * or MDTM objective, an ineligible planet and a forced generic kernel run the
+ * generic kernel's pinned variant set by set (path 0); a forced fast kernel
+ * with such an objective and a forced group kernel are BOTE_E_ARG.
+ * max_blocks caps the batch kernel's grid (0: no cap), for a shared device. */
+typedef struct bote_batch bote_batch;
+int bote_batch_create(const bote_planet* p, const uint32_t* servers, uint32_t ns,
+                      const uint32_t* clients, uint32_t nc, uint32_t n,
+                      const uint32_t* pinned, uint32_t n_sets, uint32_t n_pinned, uint32_t max_blocks,
+                      const bote_objective* objs, uint32_t n_obj, uint32_t K,
+                      const bote_ranking_params* rp, int digest, int kernel, bote_batch** out);
+/* Asynchronous on `hip_stream`, like bote_sweep_launch. */
+int bote_batch_launch(bote_batch* b, void* hip_stream);
+/* Synchronises `hip_stream`.  out: n_sets x n_obj x K records (padding past a
+ * list's count), out_count: n_sets x n_obj, out_valid and out_digest: n_sets
+ * (any may be null).  When the last launch deferred any config (a leader COV
+ * near-tie; the batch kernel only counts them), every set is recomputed here
+ * on the generic kernel's pinned variant before the copy: no result is built
+ * from a truncated queue. */
+int bote_batch_result(bote_batch* b, void* hip_stream, bote_topk_record* out, uint32_t* out_count,
+                      uint64_t* out_valid, uint64_t* out_digest);
+/* Configs the last launch deferred, over all sets (0 on the generic path).  Synchronises `hip_stream`. */
+int bote_batch_deferred(bote_batch* b, void* hip_stream, uint64_t* out);
+/* 0 generic, 1 fast (bote_sweep_is_fast's values). */
+int bote_batch_path(const bote_batch* b, int* out);
+/* Kernel-only time of the last launch in ms: the batch kernel, or the sum of the generic path's kernels. */
+int bote_batch_last_kernel_ms(bote_batch* b, float* out_ms);
+/* The unit plan: slices per set, units (n_sets x slices) and the batch kernel's grid (any may be null). */
+int bote_batch_plan(const bote_batch* b, uint32_t* out_slices, uint64_t* out_units, uint32_t* out_grid);
+/* May be called after the planet is destroyed, like bote_sweep_destroy. */
+int bote_batch_destroy(bote_batch* b);
 
 /* ------------------------------------------------ multi-device search --- */
 /* The exhaustive search over colex ranks [rank_begin, rank_end) sharded over

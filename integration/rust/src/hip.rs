@@ -52,6 +52,10 @@ pub struct bote_sweep {
     _p: [u8; 0],
 }
 #[repr(C)]
+pub struct bote_batch {
+    _p: [u8; 0],
+}
+#[repr(C)]
 #[derive(Clone, Copy, Debug)]
 pub struct bote_objective {
     pub kind: u32,
@@ -159,6 +163,19 @@ extern "C" {
                                     objs: *const bote_objective, n_obj: u32, k: u32,
                                     rp: *const bote_ranking_params, digest: c_int, kernel: c_int,
                                     out: *mut *mut bote_sweep) -> c_int;
+    pub fn bote_batch_create(p: *const bote_planet, servers: *const u32, ns: u32, clients: *const u32, nc: u32,
+                             n: u32, pinned: *const u32, n_sets: u32, n_pinned: u32, max_blocks: u32,
+                             objs: *const bote_objective, n_obj: u32, k: u32, rp: *const bote_ranking_params,
+                             digest: c_int, kernel: c_int, out: *mut *mut bote_batch) -> c_int;
+    pub fn bote_batch_launch(b: *mut bote_batch, stream: *mut c_void) -> c_int;
+    pub fn bote_batch_result(b: *mut bote_batch, stream: *mut c_void, out: *mut bote_topk_record,
+                             out_count: *mut u32, out_valid: *mut u64, out_digest: *mut u64) -> c_int;
+    pub fn bote_batch_deferred(b: *mut bote_batch, stream: *mut c_void, out: *mut u64) -> c_int;
+    pub fn bote_batch_path(b: *const bote_batch, out: *mut c_int) -> c_int;
+    pub fn bote_batch_last_kernel_ms(b: *mut bote_batch, out_ms: *mut f32) -> c_int;
+    pub fn bote_batch_plan(b: *const bote_batch, out_slices: *mut u32, out_units: *mut u64, out_grid: *mut u32)
+        -> c_int;
+    pub fn bote_batch_destroy(b: *mut bote_batch) -> c_int;
 }
 
 /// Turns a status code into the panic the reference raises at the same place
