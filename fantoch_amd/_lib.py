@@ -67,6 +67,7 @@ EXPORTS = [
     "bote_sweep_create_pinned", "bote_pinned_total", "bote_pinned_config",
     "bote_batch_create", "bote_batch_launch", "bote_batch_result", "bote_batch_deferred", "bote_batch_path",
     "bote_batch_last_kernel_ms", "bote_batch_plan", "bote_batch_destroy",
+    "bote_batch_create_bounded", "bote_batch_limits", "bote_mean_decrease_limit",
 ]
 KERNELS = {None: 0, "auto": 0, "generic": 1, "fast": 2, "group": 3}
 
@@ -200,6 +201,10 @@ def lib():
         L.bote_batch_last_kernel_ms.argtypes = [_vp, C.POINTER(C.c_float)]
         L.bote_batch_plan.argtypes = [_vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
         L.bote_batch_destroy.argtypes = [_vp]
+    if hasattr(L, "bote_batch_create_bounded"):  # (the same)
+        L.bote_batch_create_bounded.argtypes = L.bote_batch_create.argtypes[:-1] + [_u64p, C.POINTER(_vp)]
+        L.bote_batch_limits.argtypes = [_vp, _u32p]
+        L.bote_mean_decrease_limit.argtypes = [C.c_uint64, C.c_uint32, C.c_double, C.POINTER(C.c_uint32)]
     if hasattr(L, "bote_percentile_index"):  # (absent from an older BOTE_LIB_PATH build loaded for A/B timing)
         L.bote_percentile_index.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_int)]
     _LIB = L
@@ -242,6 +247,15 @@ def percentile_index(bp: int, count: int):
     idx, whole = C.c_uint32(0), C.c_int(0)
     check(lib().bote_percentile_index(bp, count, C.byref(idx), C.byref(whole)))
     return idx.value, bool(whole.value)
+
+
+def mean_decrease_limit(prev_s1: int, count: int, min_mean_decrease: float) -> int:
+    """The limit L of Search::min_mean_decrease on one slot (search.rs:403-419): over `count` values,
+    fl(prev_s1 / count) - fl(s1 / count) >= min_mean_decrease exactly for the sums 0 <= s1 < L
+    (0: none passes; 2^27: every sum the library admits)."""
+    out = C.c_uint32(0)
+    check(lib().bote_mean_decrease_limit(prev_s1, count, float(min_mean_decrease), C.byref(out)))
+    return out.value
 
 
 def colex_unrank(rank: int, n: int, ns: int) -> np.ndarray:

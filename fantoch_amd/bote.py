@@ -934,12 +934,17 @@ class PinnedBatch:
     the same size m, 1 <= m < n, of positions into `servers` (any order; sets may
     be equal or overlap).  result() gives, per set, what Sweep(pinned=set) gives
     over its whole rank space.  Base key set.  max_blocks caps the kernel's grid
-    (0: the device's)."""
+    (0: the device's).
+    prev_sums (B x 2: each set's exact Atlas Input sums, slots AF1 and AF2, as
+    eval_configs gives them for the set's config) makes it a bounded batch
+    (bote_batch_create_bounded): a superset is valid only if, beside
+    compute_score's tests, its Atlas means lie `ranking.min_mean_decrease` below
+    the set's (Search::min_mean_decrease, for f in ft_metric.fs(n - 2))."""
 
     def __init__(self, dp: DevicePlanet, servers: Sequence[int], clients: Sequence[int], n: int,
                  pinned_sets: Sequence[Sequence[int]], objectives=DEFAULT_OBJECTIVES, K: int = 100,
                  ranking: Optional[RankingParams] = DEFAULT_RANKING, digest: bool = False,
-                 kernel: Optional[str] = None, max_blocks: int = 0):
+                 kernel: Optional[str] = None, max_blocks: int = 0, prev_sums=None):
         self.dp, self.n, self.K = dp, n, K
         self.servers, self.clients = u32(servers), u32(clients)
         sets = [u32(s) for s in pinned_sets]
@@ -954,9 +959,16 @@ class PinnedBatch:
         rp = C.byref(_lib.ranking_params_c(ranking)) if ranking is not None else None
         self.h = None
         h = C.c_void_p()
-        check(lib().bote_batch_create(dp.h, self.servers, len(self.servers), self.clients, len(self.clients), n,
-                                      self.pinned_sets.reshape(-1), B, m, max_blocks, objs, len(self.objectives), K, rp,
-                                      1 if digest else 0, _lib.KERNELS[kernel], C.byref(h)))
+        args = (dp.h, self.servers, len(self.servers), self.clients, len(self.clients), n,
+                self.pinned_sets.reshape(-1), B, m, max_blocks, objs, len(self.objectives), K, rp,
+                1 if digest else 0, _lib.KERNELS[kernel])
+        if prev_sums is None:
+            check(lib().bote_batch_create(*args, C.byref(h)))
+        else:
+            prev = np.ascontiguousarray(np.asarray(prev_sums, dtype=np.uint64).reshape(-1))
+            if len(prev) != 2 * B:
+                raise ValueError("prev_sums holds two sums (AF1, AF2) per pinned set")
+            check(lib().bote_batch_create_bounded(*args, prev, C.byref(h)))
         self.h = h
 
     @classmethod
@@ -992,6 +1004,13 @@ class PinnedBatch:
             recs = recs.reshape(B, no, K, 2)
         return [SweepResult([list(map(tuple, recs[b, o, :cnt[b, o]].tolist())) for o in range(no)],
                             int(valid[b]), int(digest[b])) for b in range(B)]
+
+    def limits(self) -> np.ndarray:
+        """B x 2: per set the exclusive bounds on a valid config's S1 of slots AF1 and AF2
+        (0xFFFFFFFF: no bound; every word of a batch without prev_sums)."""
+        out = np.zeros(2 * len(self.pinned_sets), np.uint32)
+        check(lib().bote_batch_limits(self.h, out))
+        return out.reshape(-1, 2)
 
     def deferred(self, stream: Optional[int] = None) -> int:
         """Configs the last launch deferred to the exact generic kernel, over all sets."""

@@ -21,6 +21,9 @@ main.rs:31-60).  Subcommands expose them, and the sweep the hot path serves:
                         [--objectives default|config5|mean:af1,cov:af1,max:af1,p95:af1,p99.9:e,mdtm:af1,score,...]
                         [--keys base|tempo-all-leaders] [--gpus G] [--rank-begin B --rank-end E]
                         [--pinned a,b | --pinned 3,9 | --pinned-sets "a,b;c,d"]
+  python -m fantoch_amd evolve (--synthetic R [--seed S] | --lat-dir D [--input R13C13|R17C17|R20C20])
+                        [--min-n 3] [--max-n 13] [--beam B] [-K 100] [--ranking 110,35,0,15] [--ft F1F2]
+                        [--chains 1]
 """
 from __future__ import annotations
 
@@ -266,6 +269,40 @@ def sweep(args, out=sys.stdout):
     return block(res, pinned)
 
 
+def evolve(args, out=sys.stdout) -> int:
+    """The streaming evolving search (evolve.py): the best chains' scores and, per
+    level, the region names, then whether the search was exhaustive (then the
+    chains are Search::sorted_evolving_configs').  No chain: exit 101, as `main`."""
+    import numpy as np
+
+    from .bote import DevicePlanet, FTMetric, RankingParams, SearchInput
+    from .evolve import Evolve
+
+    planet = _planet(args)
+    if args.input and not args.synthetic:
+        regions, _ = SearchInput(args.input).get_inputs(args.max_n, planet)
+        srv = np.array(sorted(planet.idx(r) for r in regions), dtype=np.uint32)
+    else:
+        srv = np.arange(planet.R, dtype=np.uint32)
+    a, b, c, d = (float(x) for x in args.ranking.split(","))
+    params = RankingParams(a, b, c, d, args.min_n, args.max_n, FTMetric[args.ft])
+    res = Evolve(DevicePlanet(planet, args.device), srv, srv, params, beam=args.beam, K=args.K).run()
+    for lv in res.levels:
+        print(f"level n={lv.n}: frontier {lv.frontier}, batches {lv.batches}, chains {lv.chains}, "
+              f"kernel {lv.kernel_ms:.3f} ms", file=out)
+    print(f"chains: {len(res.chains)}", file=out)
+    print("exhaustive: " + ("yes (the chains are sorted_evolving_configs')" if res.exhaustive
+                            else "no (a list came back full or the beam cut)"), file=out)
+    if not res.chains:
+        print("error: no evolving config chain", file=sys.stderr)
+        return 101
+    for chain in res.chains[:args.chains]:
+        print(f"score: {rust_f64(chain[0])}", file=out)
+        for n, ids in zip(res.ns, res.configs_of(chain)):
+            print(f"n={n}: " + ",".join(planet.names[i] for i in ids), file=out)
+    return 0
+
+
 def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(prog="python -m fantoch_amd", description=__doc__.split("\n\n")[0], allow_abbrev=False)
     sub = ap.add_subparsers(dest="cmd")
@@ -317,6 +354,19 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--pinned-sets", default=None,
                    help="';'-separated --pinned lists of one size: one launch sweeps every set, one block per set")
     p.add_argument("--compact", action="store_true")
+    p = sub.add_parser("evolve", allow_abbrev=False, help="streaming evolving search: bounded pinned batches and a beam")
+    planet_flags(p, synthetic=True)
+    p.add_argument("--input", default=None, choices=["R13C13", "R17C17", "R20C20"],
+                   help="the reference's server/client set of a GCP planet (default: every region)")
+    p.add_argument("--min-n", type=int, default=3)
+    p.add_argument("--max-n", type=int, default=13)
+    p.add_argument("--beam", type=int, default=None, help="partial chains kept after each level (default: all)")
+    p.add_argument("-K", "--K", dest="K", type=int, default=100, help="records kept per list")
+    p.add_argument("--ranking", default="110,35,0,15",
+                   help="min_mean_fpaxos_improv,min_mean_epaxos_improv,min_fairness_fpaxos_improv,"
+                        "min_mean_decrease")
+    p.add_argument("--ft", default="F1F2", choices=["F1", "F1F2"])
+    p.add_argument("--chains", type=int, default=1, help="best chains to print")
     return ap
 
 
@@ -333,4 +383,6 @@ def main(argv: Optional[Sequence[str]] = None, out=sys.stdout) -> int:
         config_stats(args, out)
     elif cmd == "sweep":
         sweep(args, out)
+    elif cmd == "evolve":
+        return evolve(args, out)
     return 0

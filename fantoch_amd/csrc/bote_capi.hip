@@ -165,6 +165,12 @@ int bote_percentile_index(uint32_t bp, uint32_t count, uint32_t* out_idx, int* o
   return BOTE_OK;
 }
 
+int bote_mean_decrease_limit(uint64_t prev_s1, uint32_t count, double min_mean_decrease, uint32_t* out_limit) {
+  ARG_TRY(check_mean_limit_args(prev_s1, count, out_limit));
+  *out_limit = mean_decrease_limit(prev_s1, count, min_mean_decrease);
+  return BOTE_OK;
+}
+
 int bote_colex_unrank(uint64_t rank, uint32_t n, uint32_t ns, uint32_t* out) {
   if (!out || n > ns) return fail(BOTE_E_ARG, "bad unrank arguments");
   if (!colex_unrank(rank, n, ns, out)) return fail(BOTE_E_ARG, "rank out of range");

@@ -12,7 +12,10 @@
 //         positions, on the generic path and for the recompute of a batch that
 //         deferred configs.
 // What the batch adds is the set table, the per-set list slots and counters
-// and the B result blocks.
+// and the B result blocks.  A bounded batch (bote_batch_create_bounded, DESIGN.md
+// §4 "Streaming evolving search") also fills each set's two limits
+// (PinArgs::lim): they travel in the set table to the batch kernel and, by
+// value, with every per-set launch of `gen`.
 #include "bote_capi.hpp"
 
 using bote::EvalArgs;
@@ -79,20 +82,20 @@ int launch_batch_fast(bote_batch* b, hipStream_t st) {
   return BOTE_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int bote_batch_create(const bote_planet* p, const uint32_t* servers, uint32_t ns, const uint32_t* clients, uint32_t nc,
-                      uint32_t n, const uint32_t* pinned, uint32_t n_sets, uint32_t n_pinned, uint32_t max_blocks,
-                      const bote_objective* objs, uint32_t n_obj, uint32_t K, const bote_ranking_params* rp, int digest,
-                      int kernel, bote_batch** out) {
+// bote_batch_create and, with `bounded`, bote_batch_create_bounded: prev_s1
+// holds each set's previous-level Atlas sums, turned into the set's limits
+// (PinArgs::lim) with rp's min_mean_decrease and ft_metric
+int batch_create(const bote_planet* p, const uint32_t* servers, uint32_t ns, const uint32_t* clients, uint32_t nc,
+                 uint32_t n, const uint32_t* pinned, uint32_t n_sets, uint32_t n_pinned, uint32_t max_blocks,
+                 const bote_objective* objs, uint32_t n_obj, uint32_t K, const bote_ranking_params* rp, int digest,
+                 int kernel, bool bounded, const uint64_t* prev_s1, bote_batch** out) {
   DevGuard dev_guard;  // the caller's current device is restored on return
   bool has_score = false;
   if (!out) return fail(BOTE_E_ARG, "out is null");
   ARG_TRY(check_sweep_args(p ? p->R : 0, servers, ns, clients, nc, n, objs, n_obj, K, rp, kernel, 0, has_score));
   ARG_TRY(check_batch_args(ns, n, pinned, n_sets, n_pinned, 0));
   ARG_TRY(check_pinned_args(ns, n, pinned, n_pinned, kernel, 0));  // (a forced group kernel)
+  if (bounded) ARG_TRY(check_bounded_args(prev_s1, n_sets, nc, rp));
   auto* b = new bote_batch();
   auto cleanup = [&](int code) {
     const std::string msg = g_err;  // (destroying the inner sweeps must not lose the text)
@@ -114,6 +117,7 @@ int bote_batch_create(const bote_planet* p, const uint32_t* servers, uint32_t ns
     z.pin_n = n_pinned;
     std::copy(pinned + (size_t)i * n_pinned, pinned + (size_t)(i + 1) * n_pinned, z.pin);
     std::sort(z.pin, z.pin + n_pinned);
+    if (bounded) batch_limits(prev_s1 + 2 * (size_t)i, n, nc, rp->min_mean_decrease, rp->ft_metric, z.lim);
   }
   int rc;
   if (kernel != BOTE_KERNEL_GENERIC) {
@@ -157,6 +161,33 @@ int bote_batch_create(const bote_planet* p, const uint32_t* servers, uint32_t ns
   if (hipEventCreateWithFlags(&b->done, hipEventDisableTiming) != hipSuccess)
     return cleanup(fail(BOTE_E_DEVICE, "hipEventCreate"));
   *out = b;
+  return BOTE_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bote_batch_create(const bote_planet* p, const uint32_t* servers, uint32_t ns, const uint32_t* clients, uint32_t nc,
+                      uint32_t n, const uint32_t* pinned, uint32_t n_sets, uint32_t n_pinned, uint32_t max_blocks,
+                      const bote_objective* objs, uint32_t n_obj, uint32_t K, const bote_ranking_params* rp, int digest,
+                      int kernel, bote_batch** out) {
+  return batch_create(p, servers, ns, clients, nc, n, pinned, n_sets, n_pinned, max_blocks, objs, n_obj, K, rp, digest,
+                      kernel, false, nullptr, out);
+}
+
+int bote_batch_create_bounded(const bote_planet* p, const uint32_t* servers, uint32_t ns, const uint32_t* clients,
+                              uint32_t nc, uint32_t n, const uint32_t* pinned, uint32_t n_sets, uint32_t n_pinned,
+                              uint32_t max_blocks, const bote_objective* objs, uint32_t n_obj, uint32_t K,
+                              const bote_ranking_params* rp, int digest, int kernel, const uint64_t* prev_s1,
+                              bote_batch** out) {
+  return batch_create(p, servers, ns, clients, nc, n, pinned, n_sets, n_pinned, max_blocks, objs, n_obj, K, rp, digest,
+                      kernel, true, prev_s1, out);
+}
+
+int bote_batch_limits(const bote_batch* b, uint32_t* out) {
+  if (!b || !out) return fail(BOTE_E_ARG, "null argument");
+  for (uint32_t i = 0; i < b->n_sets; ++i) std::copy(b->sets[i].lim, b->sets[i].lim + 2, out + 2 * (size_t)i);
   return BOTE_OK;
 }
 

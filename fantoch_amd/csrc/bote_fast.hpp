@@ -32,18 +32,21 @@ __device__ __forceinline__ void defer_rank(const FastArgs& a, uint64_t rank) {
 // percentile objective's, from the caller's sorted lists; with FAST_MDTM an
 // MDTM objective's, from the caller's second pass (such a sweep has no MAX or
 // percentile objective); with FAST_PLAIN no objective has those kinds.
+// `pre_valid` seeds the validity: a bounded batch passes its limits' verdict
+// (PinArgs::lim), one more term of the conjunction; a config it rejects is
+// invalid whatever its COV decisions say, so it does not defer on them.
 template <int N, int TAIL = FAST_PLAIN>
 __device__ __forceinline__ bool finish_config(const FastArgs& a, const Mom (&mom)[NSLOT], double vcol_lead,
                                               uint32_t lead_member, uint64_t rank, const Rec* thr, double pnc1,
                                               double pnc2, uint64_t& valid_cnt, uint64_t& digest,
-                                              uint64_t (&key)[MAXOBJ], bool (&ok)[MAXOBJ]) {
+                                              uint64_t (&key)[MAXOBJ], bool (&ok)[MAXOBJ], bool pre_valid = true) {
   using QC = QCfg<N>;
   const uint32_t nc = a.nc;
   bool amb = false;
   bool valid = false;
   const int fcap = min(N / 2, a.ft_metric);
   if (a.want_score && !ABLATE(a, 8)) {
-    valid = true;
+    valid = pre_valid;
 #pragma unroll
     for (int f = 1; f <= 2; ++f) {
       if (f > fcap) break;

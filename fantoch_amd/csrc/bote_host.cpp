@@ -751,6 +751,53 @@ BatchPlan batch_plan(uint32_t ns, uint32_t n, uint32_t m, uint32_t n_sets, uint3
   return p;
 }
 
+bool mean_decrease_passes(uint64_t prev_s1, uint64_t s1, uint32_t count, double min_mean_decrease) {
+  // (volatile: each step is one rounded f64 operation whatever the flags)
+  volatile double c = (double)count;
+  volatile double prev_mean = (double)prev_s1 / c;
+  volatile double mean = (double)s1 / c;
+  volatile double improv = prev_mean - mean;
+  return improv >= min_mean_decrease;
+}
+
+uint32_t mean_decrease_limit(uint64_t prev_s1, uint32_t count, double min_mean_decrease) {
+  // the passing sums are a prefix of [0, MEAN_SUM_END): its length
+  uint64_t lo = 0, hi = MEAN_SUM_END;  // every s1 < lo passes, no s1 in [hi, MEAN_SUM_END) does
+  while (lo < hi) {
+    const uint64_t mid = lo + (hi - lo) / 2;
+    if (mean_decrease_passes(prev_s1, mid, count, min_mean_decrease)) lo = mid + 1;
+    else hi = mid;
+  }
+  return (uint32_t)lo;
+}
+
+void batch_limits(const uint64_t* prev_s1, uint32_t n, uint32_t nc, double min_mean_decrease, int ft_metric,
+                  uint32_t* out_lim) {
+  // FTMetric::fs(n - 2): f = 1 .. min((n - 2) / 2, 1 or 2)
+  const uint32_t minority = n >= 2 ? (n - 2) / 2 : 0;
+  const uint32_t fcap = std::min<uint32_t>(minority, ft_metric == BOTE_FT_F1F2 ? 2 : 1);
+  for (uint32_t f = 1; f <= 2; ++f)
+    out_lim[f - 1] = f <= fcap ? mean_decrease_limit(prev_s1[f - 1], nc, min_mean_decrease) : MEAN_NO_BOUND;
+}
+
+Status check_mean_limit_args(uint64_t prev_s1, uint32_t count, const uint32_t* out_limit) {
+  if (!out_limit) return fail(BOTE_E_ARG, "out_limit is null");
+  if (count == 0) return fail(BOTE_E_ARG, "a mean needs count >= 1");
+  if (prev_s1 >= MEAN_SUM_END) return fail(BOTE_E_RANGE, "previous sum must be below 2^27");
+  return OK;
+}
+
+Status check_bounded_args(const uint64_t* prev_s1, uint32_t n_sets, uint32_t nc, const bote_ranking_params* rp) {
+  if (!rp) return fail(BOTE_E_ARG, "a bounded batch needs ranking params");
+  if (!prev_s1) return fail(BOTE_E_ARG, "prev_s1 is null");
+  if (nc == 0) return fail(BOTE_E_ARG, "a bounded batch needs clients");
+  for (uint32_t b = 0; b < n_sets; ++b)
+    for (uint32_t f = 0; f < 2; ++f)
+      if (prev_s1[2 * (size_t)b + f] >= MEAN_SUM_END)
+        return fail(BOTE_E_RANGE, "pinned set " + std::to_string(b) + ": previous sum must be below 2^27");
+  return OK;
+}
+
 Status check_rank_span_total(uint64_t total, uint64_t rank_begin, uint64_t rank_end) {
   if (rank_begin > rank_end || rank_end > total) return fail(BOTE_E_ARG, "rank range out of bounds");
   return OK;

@@ -292,6 +292,34 @@ struct BatchPlan {
   uint32_t runlen = 0;
 };
 BatchPlan batch_plan(uint32_t ns, uint32_t n, uint32_t m, uint32_t n_sets, uint32_t grid_cap);
+// ----------------------------------------------------- bounded batches --
+// The reference's filter between two levels of an evolving chain
+// (Search::min_mean_decrease, search.rs:403-419; DESIGN.md §4 "Streaming
+// evolving search"): for f in FTMetric::fs(n - 2), on the Atlas f Input slot,
+//   fl(prev_s1 / count) - fl(s1 / count) >= min_mean_decrease
+// (Histogram::mean_improv: two rounded divisions, one rounded subtraction).
+// fl(s1 / count) is non-decreasing in s1 and the rounded difference
+// non-increasing in its subtrahend, so the passing sums are exactly s1 < limit.
+// MEAN_SUM_END: every S1 the library admits is below it (4096 clients of at
+// most 2 * 16383); MEAN_NO_BOUND: the kernels' "no bound" (PinArgs::lim).
+constexpr uint64_t MEAN_SUM_END = 1ull << BOTE_MDTM_SUM_BITS;
+constexpr uint32_t MEAN_NO_BOUND = 0xFFFFFFFFu;
+static_assert((uint64_t)BOTE_MAX_CLIENTS * 2 * 16383 < MEAN_SUM_END, "every S1 is below the search range's end");
+// The predicate itself, each step one rounded f64 operation (count >= 1).
+bool mean_decrease_passes(uint64_t prev_s1, uint64_t s1, uint32_t count, double min_mean_decrease);
+// The least s1 in [0, MEAN_SUM_END] that does not pass (MEAN_SUM_END: all
+// pass; 0: none does, a NaN threshold among the reasons), by binary search.
+uint32_t mean_decrease_limit(uint64_t prev_s1, uint32_t count, double min_mean_decrease);
+// A set's two limits (SLOT_AF1, SLOT_AF2) for configs of size n from its
+// previous level's sums prev_s1[0..1]: MEAN_NO_BOUND where f is not in fs(n - 2).
+void batch_limits(const uint64_t* prev_s1, uint32_t n, uint32_t nc, double min_mean_decrease, int ft_metric,
+                  uint32_t* out_lim);
+// bote_mean_decrease_limit: a null out, count 0, a sum >= MEAN_SUM_END.
+Status check_mean_limit_args(uint64_t prev_s1, uint32_t count, const uint32_t* out_limit);
+// bote_batch_create_bounded, after bote_batch_create's checks.  In order: null
+// ranking params, a null prev_s1, no clients, then per set, lowest index first,
+// a sum >= MEAN_SUM_END, naming the set.
+Status check_bounded_args(const uint64_t* prev_s1, uint32_t n_sets, uint32_t nc, const bote_ranking_params* rp);
 // rank_begin <= rank_end <= `total` (a pinned sweep's pinned_total).
 Status check_rank_span_total(uint64_t total, uint64_t rank_begin, uint64_t rank_end);
 // bote_evolving_chains' six levels (n = 3, 5, .., 13): arrays present where a

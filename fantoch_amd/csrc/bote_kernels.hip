@@ -710,6 +710,9 @@ __global__ void __launch_bounds__(256) eval_kernel(std::conditional_t<PIN, PinEv
       CfgOut<N, X, PASSES> r;
       if (have) {
         eval_config<N, FULL, X, PASSES>(a, s, p, sorted_in, rank - a.rb, r);
+        if constexpr (PIN)  // a bounded batch's limits (PinArgs::lim; no bound otherwise)
+          r.valid = r.valid && r.mom[SLOT_AF1].s1 < a.pz.lim[0] &&
+                    (QCfg<N>::maxf < 2 || r.mom[SLOT_AF2].s1 < a.pz.lim[1]);
         if (r.valid) ++valid_cnt;
         if (a.want_digest) {
           uint32_t h = 0;

@@ -194,9 +194,17 @@ struct FastArgs {
 // A pinned sweep's fixed members (bote_pinned.hpp).  The launchers of the fast
 // and the generic kernel take a pointer to it (null: not pinned), run their
 // pinned variant and append it to the kernel's arguments.
+// lim: a bounded batch's limits (DESIGN.md §4 "Streaming evolving search"),
+// exclusive, on the config's S1 of SLOT_AF1 and SLOT_AF2: one more term of
+// compute_score validity, S1 < lim.  PIN_NO_BOUND passes every sum (S1 < 2^27).
+// The batch variant of the fast kernel and the pinned variant of the generic
+// kernel read them; PIN_NONE and PIN_ONE never do.  The last words of every
+// kernarg struct that ends in a PinArgs.
+constexpr uint32_t PIN_NO_BOUND = 0xFFFFFFFFu;
 struct PinArgs {
   uint32_t pin_n;      // m
   uint32_t pin[MAXN];  // the pinned positions, ascending; 0 from pin_n on
+  uint32_t lim[2] = {PIN_NO_BOUND, PIN_NO_BOUND};
 };
 // A batch of pinned sweeps (DESIGN.md §4 "Batched pinned sweeps"): n_sets
 // pinned sets of one size, each swept over its whole pinned-rank space in one

@@ -72,6 +72,13 @@ __host__ __device__ inline FastLds fast_layout(const FastArgs& a, int N, int NLW
   return l;
 }
 
+// The batch variant keeps the unit's two limits (PinArgs::lim) in the last two
+// of the 12 words reserved at `cnt` (16-byte aligned; the top-K uses 1 + MAXOBJ):
+// no variant's layout changes.
+constexpr int BATCH_LIM_WORD = 10;
+static_assert(1 + MAXOBJ <= BATCH_LIM_WORD && (BATCH_LIM_WORD + 2) * 4 <= 48 && BATCH_LIM_WORD % 2 == 0,
+              "the limits follow the top-K counters inside the reserved 48 bytes, 8-byte aligned");
+
 size_t fast_smem_bytes(const FastArgs& a, uint32_t n, int tail) {
   int nl = 0;
   switch (n) {
@@ -567,11 +574,16 @@ __global__ void __launch_bounds__(FAST_BD, 4) sweep_fast_kernel(typename Members
       zb = a.bz.sets[set];  // (uniform loads)
       dst = a.out_top + ((size_t)set * BATCH_SET_LISTS + sl) * a.n_obj * KP;
       counters = a.out_counters + 2 * (size_t)set;
+      // the unit's limits (PinArgs::lim), written once per unit into the two
+      // spare words of the top-K counters' region and read back per config:
+      // no scalar stays live over the unit for them.  (The last unit's configs
+      // are done: every wave has passed the barrier before its list dump.)
+      if (tid == 0) *(uint2*)(s.tk.cnt + BATCH_LIM_WORD) = make_uint2(zb.lim[0], zb.lim[1]);
       if (unit != blockIdx.x) {  // the last unit's list is out: a fresh top-K
         __syncthreads();
         topk_init(s.tk, a.n_obj);
-        __syncthreads();
       }
+      __syncthreads();
     }
     const uint64_t total = re - rb;
     const uint64_t njobs = (total + runlen - 1) / runlen;
@@ -622,8 +634,13 @@ __global__ void __launch_bounds__(FAST_BD, 4) sweep_fast_kernel(typename Members
             input_fpaxos(s, ld, nc, mom, tl, a, key, ok);
             colocated<N>(B, ld, rowq, qlane, cS1, cS2, mom, tl, a, key, ok);
             tl.build_keys(ld.lq2, ld.lq3, TailKeys{a, mom, key, ok});
+            bool pre_valid = true;  // BATCH: the set's limits on the Atlas sums
+            if constexpr (BATCH) {
+              const uint2 lim = *(const uint2*)(s.tk.cnt + BATCH_LIM_WORD);
+              pre_valid = (uint32_t)mom[SLOT_AF1].s1 < lim.x && (QCfg<N>::maxf < 2 || (uint32_t)mom[SLOT_AF2].s1 < lim.y);
+            }
             if (!finish_config<N, TAIL>(a, mom, s.vcol[ld.lp], ld.bi, frank, s.tk.thr, pnc1, pnc2, valid_cnt, digest,
-                                        key, ok)) {
+                                        key, ok, pre_valid)) {
               defer();
               have = false;
               TL::withdraw(ok);

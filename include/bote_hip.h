@@ -419,6 +419,30 @@ int bote_batch_create(const bote_planet* p, const uint32_t* servers, uint32_t ns
                       const uint32_t* pinned, uint32_t n_sets, uint32_t n_pinned, uint32_t max_blocks,
                       const bote_objective* objs, uint32_t n_obj, uint32_t K,
                       const bote_ranking_params* rp, int digest, int kernel, bote_batch** out);
+/* bote_batch_create with the reference's filter between two levels of an
+ * evolving chain (Search::min_mean_decrease, search.rs:403-419) as one more
+ * term of every config's validity.  prev_s1[2 b], prev_s1[2 b + 1] are the
+ * exact sums of set b's previous-level config on the Atlas Input slots
+ * (BOTE_SLOT_AF1, BOTE_SLOT_AF2; from bote_eval's out_sum), each below 2^27
+ * (BOTE_E_RANGE otherwise).  A superset of set b is valid iff it is valid for
+ * bote_batch_create and, for every f in FTMetric::fs(n - 2),
+ *   fl(prev_s1_f / nc) - fl(S1_f / nc) >= rp->min_mean_decrease
+ * in the reference's f64 arithmetic (exactly: the host turns each term into an
+ * integer limit, bote_mean_decrease_limit).  The filter changes a set's valid
+ * count and the configs offered to SCORE objectives; MEAN and COV lists and the
+ * digest are those of bote_batch_create.  rp must not be null, with or
+ * without a SCORE objective.  A batch of one set is the bounded pinned sweep. */
+int bote_batch_create_bounded(const bote_planet* p, const uint32_t* servers, uint32_t ns,
+                              const uint32_t* clients, uint32_t nc, uint32_t n,
+                              const uint32_t* pinned, uint32_t n_sets, uint32_t n_pinned, uint32_t max_blocks,
+                              const bote_objective* objs, uint32_t n_obj, uint32_t K,
+                              const bote_ranking_params* rp, int digest, int kernel,
+                              const uint64_t* prev_s1, bote_batch** out);
+/* The sets' limits: out[2 b], out[2 b + 1] are the exclusive bounds on a
+ * config's S1 of BOTE_SLOT_AF1 and BOTE_SLOT_AF2 (0: nothing passes;
+ * 0xFFFFFFFF: no bound, which is every word of an unbounded batch and the
+ * f = 2 word when 2 is not in FTMetric::fs(n - 2)).  Host only. */
+int bote_batch_limits(const bote_batch* b, uint32_t* out);
 /* Asynchronous on `hip_stream`, like bote_sweep_launch. */
 int bote_batch_launch(bote_batch* b, void* hip_stream);
 /* Synchronises `hip_stream`.  out: n_sets x n_obj x K records (padding past a
@@ -499,6 +523,13 @@ int bote_pinned_config(uint64_t pinned_rank, uint32_t n, uint32_t ns, const uint
  * p * count is that integer exactly (the percentile is then the midpoint of
  * s[idx-1] and s[idx]).  BOTE_E_ARG unless 1 <= bp <= 9999 and count >= 1. */
 int bote_percentile_index(uint32_t bp, uint32_t count, uint32_t* out_idx, int* out_whole);
+/* Search::min_mean_decrease's test on one slot (search.rs:403-419,
+ * Histogram::mean_improv) as an integer limit (host only): over `count` values,
+ * fl(prev_s1 / count) - fl(s1 / count) >= min_mean_decrease holds exactly for
+ * the sums s1 < *out_limit, 0 <= s1 < 2^27 (the left side is non-increasing in
+ * s1).  0: no sum passes; 2^27: every sum does.  BOTE_E_ARG for a null
+ * out_limit or count 0, BOTE_E_RANGE for prev_s1 >= 2^27. */
+int bote_mean_decrease_limit(uint64_t prev_s1, uint32_t count, double min_mean_decrease, uint32_t* out_limit);
 
 #ifdef __cplusplus
 }

@@ -176,6 +176,13 @@ extern "C" {
     pub fn bote_batch_plan(b: *const bote_batch, out_slices: *mut u32, out_units: *mut u64, out_grid: *mut u32)
         -> c_int;
     pub fn bote_batch_destroy(b: *mut bote_batch) -> c_int;
+    pub fn bote_batch_create_bounded(p: *const bote_planet, servers: *const u32, ns: u32, clients: *const u32,
+                                     nc: u32, n: u32, pinned: *const u32, n_sets: u32, n_pinned: u32,
+                                     max_blocks: u32, objs: *const bote_objective, n_obj: u32, k: u32,
+                                     rp: *const bote_ranking_params, digest: c_int, kernel: c_int,
+                                     prev_s1: *const u64, out: *mut *mut bote_batch) -> c_int;
+    pub fn bote_batch_limits(b: *const bote_batch, out: *mut u32) -> c_int;
+    pub fn bote_mean_decrease_limit(prev_s1: u64, count: u32, min_mean_decrease: f64, out_limit: *mut u32) -> c_int;
 }
 
 /// Turns a status code into the panic the reference raises at the same place

@@ -13,6 +13,12 @@ process, warm, median of `--reps` with min .. max, one JSON line:
   unpinned_kernel_ms  sweep_fast_kernel<7> (forced fast, unpinned) over a rank
                   range of the same total size
   lane_utilisation    configs of a set / lane slots of its unit's pass
+  scored_kernel_ms    the batch kernel over the same sets with [SCORE, MEAN af1,
+                  MEAN ff1] and the default ranking (validity is computed)
+  bounded_kernel_ms   the same as a bounded batch (prev_sums: the bases' Atlas
+                  sums, DESIGN.md §4 "Streaming evolving search"); null on a
+                  library without bote_batch_create_bounded (BOTE_LIB_PATH)
+  scored_valid, bounded_valid  valid configs over all sets
 
 The two paths' results are compared before anything is timed.
 
@@ -30,7 +36,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from fantoch_amd import _lib  # noqa: E402
-from fantoch_amd.bote import DevicePlanet, PinnedBatch, Sweep  # noqa: E402
+from fantoch_amd.bote import DEFAULT_RANKING, DevicePlanet, PinnedBatch, Sweep, eval_configs  # noqa: E402
 from fantoch_amd.planet import Planet  # noqa: E402
 
 
@@ -92,6 +98,25 @@ def main():
         un.result()
         if i >= args.warmup:
             ums.append(un.kernel_ms())
+    # the scored batch, and the bounded one beside it (alternating)
+    sobjs = [(_lib.OBJ_SCORE, 0)] + objs
+    skw = dict(K=100, ranking=DEFAULT_RANKING, digest=False, max_blocks=args.max_blocks)
+    scored = PinnedBatch(dp, srv, srv, 7, sets, sobjs, **skw)
+    bounded = None
+    if hasattr(_lib.lib(), "bote_batch_create_bounded"):
+        prev = eval_configs(dp, srv, srv, 5, configs=np.asarray(sets, dtype=np.uint32), values=False).s1[:, [0, 2]]
+        bounded = PinnedBatch(dp, srv, srv, 7, sets, sobjs, prev_sums=prev, **skw)
+    sms, bms, svalid, bvalid = [], [], None, None
+    for i in range(args.warmup + args.reps):
+        scored.launch()
+        svalid = sum(r.valid for r in scored.result())
+        if i >= args.warmup:
+            sms.append(scored.kernel_ms())
+        if bounded is not None:
+            bounded.launch()
+            bvalid = sum(r.valid for r in bounded.result())
+            if i >= args.warmup:
+                bms.append(bounded.kernel_ms())
     slices, units, grid = batch.plan()
     runlen = max(1, min(32, -(-(-(-per_set // slices)) // 256)))
     slots = -(-(-(-per_set // slices)) // (runlen * 256)) * runlen * 256 * slices
@@ -104,6 +129,8 @@ def main():
            "batch_ns_per_config": round(statistics.median(kms) * 1e6 / configs, 3),
            "unpinned_kernel_ms": med(ums), "unpinned_ns_per_config": round(statistics.median(ums) * 1e6 / configs, 3),
            "lane_utilisation": round(per_set / slots, 4), "runlen": runlen,
+           "scored_kernel_ms": med(sms), "bounded_kernel_ms": med(bms) if bms else None,
+           "scored_valid": svalid, "bounded_valid": bvalid,
            "lib": os.environ.get("BOTE_LIB_PATH", "tree")}
     print(json.dumps(doc))
 
