@@ -100,8 +100,9 @@ _vp = C.c_void_p
 _LIB = None
 
 
-def build(jobs: int = 2) -> str:
-    """Compile libbote_hip.so for gfx950 (hipcc cross-compiles without a GPU)."""
+def build(jobs: int = 8) -> str:
+    """Compile libbote_hip.so for gfx950 (hipcc cross-compiles without a GPU).
+    The generic kernel's five units are the long ones: 8 jobs let them overlap."""
     subprocess.run(["make", "-s", "-C", CSRC, f"-j{jobs}"], check=True)
     return LIB_PATH
 

@@ -903,7 +903,7 @@ class Sweep:
         return self.kernel_path() != "generic"
 
     def kernel_path(self) -> str:
-        """'generic' (bote_kernels.hip), 'fast' (bote_sweep.hip) or 'group' (bote_group.hip)."""
+        """'generic' (bote_eval.hpp), 'fast' (bote_sweep.hip) or 'group' (bote_group.hip)."""
         v = C.c_int()
         check(lib().bote_sweep_is_fast(self.h, C.byref(v)))
         return ("generic", "fast", "group")[v.value]

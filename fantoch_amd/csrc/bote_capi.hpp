@@ -168,7 +168,7 @@ struct bote_planet {
 
 struct bote_sweep {
   using DBuf = bote::capi::DBuf;
-  // the kernel that runs a launch: the generic one (bote_kernels.hip: any
+  // the kernel that runs a launch: the generic one (bote_eval.hpp: any
   // planet), or the fast (bote_sweep.hip) or group (bote_group.hip) kernel
   // with the generic one as the exact fixup of the configs they defer.
   // Decided by sweep_plan_fast; bote_sweep_is_fast reports its value.

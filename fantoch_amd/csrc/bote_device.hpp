@@ -71,6 +71,10 @@ struct QTab {
       if (q(t) == qq) return t;
     return -1;
   }
+  // the tables of the extended key set's Tempo slots: tiny 2f and write f + 1
+  // (tt1 and tw1 share q = 2); 0 where the key set or the slot does not exist
+  static constexpr int t_or0(int qq) { return idx(qq) < 0 ? 0 : idx(qq); }
+  static constexpr int tt1 = t_or0(2), tw1 = t_or0(2), tt2 = t_or0(4), tw2 = t_or0(3);
 };
 
 // Slots of the extended key set (include/bote_hip.h): 10 + 4 * placement +

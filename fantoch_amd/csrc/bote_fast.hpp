@@ -1,7 +1,7 @@
 // bote_fast.hpp — device pieces shared by the two fast-path sweep kernels
 // (bote_sweep.hip: every member lane-varying; bote_group.hip: wave-uniform
 // fixed members).  Both produce the same per-config results as the exact
-// generic kernel (bote_kernels.hip) or defer the config to it.
+// generic kernel (bote_eval.hpp) or defer the config to it.
 #pragma once
 #include "bote_kernels.hpp"
 

@@ -29,7 +29,7 @@
 // per-client address arithmetic is one shift-add and constant offsets fold
 // into the ds_read offset fields.
 //
-// Reference map: see bote_kernels.hip's header (Search::compute_stats,
+// Reference map: see bote_eval.hpp's header (Search::compute_stats,
 // search.rs:262-319, and the Bote functions it calls, lib.rs:38-185).
 #include "bote_fast.hpp"
 #include "bote_launch.hpp"

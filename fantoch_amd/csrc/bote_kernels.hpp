@@ -293,7 +293,7 @@ int group_occupancy(const FastArgs& a, uint32_t n, size_t shm, bool def_objectiv
 hipError_t launch_group(const FastArgs& a, uint32_t n, bool def_objectives, uint32_t grid, size_t shm, hipStream_t st,
                         hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
 
-// ---- generic exact kernel (bote_kernels.hip)
+// ---- generic exact kernel (bote_eval.hpp; its family units bote_eval_*.hip; launchers in bote_kernels.hip)
 size_t eval_smem_bytes(const EvalArgs& a, uint32_t n, uint32_t bd, bool topk);
 // The generic kernel's top-K instantiations by the passes a sweep's objectives
 // add to a config (each level has the ones below it): EVAL_PCTL one pass per

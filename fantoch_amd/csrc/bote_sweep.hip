@@ -5,7 +5,7 @@
 //   * the server set is "simple": self latency 0, latency between two servers
 //     > 0 (a colocated client's nearest server is itself)
 //   * servers in name order, >= 2 clients, min_fairness_fpaxos_improv == 0
-// Anything else runs the generic kernel (bote_kernels.hip), which is also the
+// Anything else runs the generic kernel (bote_eval.hpp), which is also the
 // exact path for the rare configs this kernel defers (COV near-ties).
 //
 // Data layout in LDS (DESIGN.md "Data layout"):
@@ -17,7 +17,7 @@
 //   qtab       per lane and member: packed leaderless quorum latencies,
 //              plane-major [member][lane] (conflict-free).
 //
-// Per config (one lane; reference functions in bote_kernels.hip's header):
+// Per config (one lane; reference functions in bote_eval.hpp's header):
 // quorum latencies by sorting each member's off-diagonal distances; FPaxos
 // leader by exact-COV comparison (variance is shift invariant, so leader l's
 // V = nc*sum(L^2) - (sum L)^2 of its column, precomputed per position); the

@@ -117,7 +117,7 @@ extern "C" {
 
 /* Sweep kernel paths (bote_sweep_create_ex); every path is exact. */
 #define BOTE_KERNEL_AUTO 0    /* group kernel when eligible, else fast, else generic */
-#define BOTE_KERNEL_GENERIC 1 /* eval_kernel (bote_kernels.hip): any planet */
+#define BOTE_KERNEL_GENERIC 1 /* eval_kernel (bote_eval.hpp): any planet */
 #define BOTE_KERNEL_FAST 2    /* sweep_fast_kernel (bote_sweep.hip) */
 #define BOTE_KERNEL_GROUP 3   /* sweep_group_kernel (bote_group.hip), n >= 4 */
 
@@ -370,7 +370,7 @@ int bote_sweep_last_kernel_ms(bote_sweep* s, float* out_ms);
  * launch since the last bote_sweep_timing_reset; synchronises on the last. */
 int bote_sweep_timing_reset(bote_sweep* s);
 int bote_sweep_timing(bote_sweep* s, float* out_total_ms, uint32_t* out_launches);
-/* Which sweep kernel runs: 0 the generic kernel (bote_kernels.hip), 1 the
+/* Which sweep kernel runs: 0 the generic kernel (bote_eval.hpp), 1 the
  * packed fast-path kernel (bote_sweep.hip), 2 the group kernel
  * (bote_group.hip).  All are exact (DESIGN.md "Kernels"). */
 int bote_sweep_is_fast(const bote_sweep* s, int* out);

@@ -8,7 +8,7 @@ D=fantoch_amd/lib_$NAME
 mkdir -p $D/obj
 H="/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wno-unused-result $FLAGS"
 # GROUP_SRC: an alternative bote_group.hip (e.g. `git show HEAD:...` for an A/B of the committed kernel)
-for f in bote_kernels bote_merge bote_sweep bote_group bote_quorums bote_chain bote_capi bote_capi_sweep bote_capi_search; do
+for f in bote_kernels bote_eval_full bote_eval_topk bote_eval_pctl bote_eval_mdtm bote_eval_pinned bote_merge bote_sweep bote_group bote_quorums bote_chain bote_capi bote_capi_sweep bote_capi_search bote_capi_batch; do
   src=fantoch_amd/csrc/$f.hip
   if [ "$f" = bote_group ] && [ -n "${GROUP_SRC:-}" ]; then src=$GROUP_SRC; fi
   # rebuild when the object is missing or older than its source or any shared

@@ -1,7 +1,7 @@
 """Percentile objectives of the streaming sweep (include/bote_hip.h
 BOTE_OBJ_PCTL): key = (2 * Histogram::percentile(p) << 32) | sum of a slot, on
 the fast kernel's sorted-list variant (bote_sweep.hip, FAST_LIST) and on the
-generic kernel (bote_kernels.hip).
+generic kernel (bote_eval.hpp).
 
 Every expected list comes from the CPU oracle: OraclePlanet.compute_stats (or
 leaderless_batch / best_leader + leader for the extended key set) over the
@@ -11,7 +11,6 @@ oracle's Histogram::percentile in tests/test_pctl_host.py) and their sum build
 the key; the lists are the K least by (key, rank).  Every comparison is exact
 equality of the full (key, rank) lists."""
 import io
-import itertools
 import json
 
 import numpy as np
@@ -21,6 +20,7 @@ import oracle as O
 from fantoch_amd import _lib, cli
 from fantoch_amd.bote import DevicePlanet, MultiDeviceSearch, Sweep, max_key, pctl_key, search_topk
 from fantoch_amd.planet import Planet
+from tests.host_keys import colex_positions, slot_values
 
 pytestmark = pytest.mark.gpu
 
@@ -38,19 +38,6 @@ def objectives(n):
     if n // 2 >= 2:
         objs += [(P(9000), AF2)]
     return objs
-
-
-def colex_positions(ns, n):
-    """Every n-subset of range(ns) as ascending positions, in colex rank order."""
-    c = np.array(list(itertools.combinations(range(ns), n)), dtype=np.uint32)
-    return c[np.lexsort(tuple(c[:, j] for j in range(n)))]  # (the last key, p[n-1], is the primary one)
-
-
-def slot_values(vals, slot, nc, n):
-    """compute_stats' columns of one slot: Input clients for slots 0..4, the n members for 5..9."""
-    if slot < 5:
-        return vals[:, slot * nc:(slot + 1) * nc]
-    return vals[:, 5 * nc + (slot - 5) * n:5 * nc + (slot - 4) * n]
 
 
 def top_of(keys, k=K, base=0):

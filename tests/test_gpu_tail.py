@@ -1,13 +1,12 @@
 """MAX (worst-client) objectives of the streaming sweep: key = (max << 32) | sum
 of a slot (include/bote_hip.h BOTE_OBJ_MAX), on the fast kernel's TAIL variant
-(bote_sweep.hip) and on the generic kernel (bote_kernels.hip).
+(bote_sweep.hip) and on the generic kernel (bote_eval.hpp).
 
 Every expected list comes from the CPU oracle: OraclePlanet.compute_stats over
 the sweep's configs in colex order gives each slot's per-client values, whose
 max and sum build the key; the lists are the K least by (key, rank).  Every
 comparison is exact equality of the full (key, rank) lists."""
 import io
-import itertools
 import json
 
 import numpy as np
@@ -18,6 +17,7 @@ from fantoch_amd import _lib, cli
 from fantoch_amd.bote import (DEFAULT_RANKING, DevicePlanet, MultiDeviceSearch, Sweep, eval_configs, max_key,
                               search_topk)
 from fantoch_amd.planet import Planet
+from tests.host_keys import colex_positions, slot_values
 
 pytestmark = pytest.mark.gpu
 
@@ -32,19 +32,6 @@ def objectives(n):
     if n // 2 >= 2:
         objs += [(MAX, AF2), (MAX, 5 + FF2)]
     return objs
-
-
-def colex_positions(ns, n):
-    """Every n-subset of range(ns) as ascending positions, in colex rank order."""
-    c = np.array(list(itertools.combinations(range(ns), n)), dtype=np.uint32)
-    return c[np.lexsort(tuple(c[:, j] for j in range(n)))]  # (the last key, p[n-1], is the primary one)
-
-
-def slot_values(vals, slot, nc, n):
-    """compute_stats' columns of one slot: Input clients for slots 0..4, the n members for 5..9."""
-    if slot < 5:
-        return vals[:, slot * nc:(slot + 1) * nc]
-    return vals[:, 5 * nc + (slot - 5) * n:5 * nc + (slot - 4) * n]
 
 
 def top_of(keys, k=K):
