@@ -443,4 +443,82 @@ int bote_test_seed(int device, const uint64_t* keys, uint32_t nsamp, uint32_t n_
   return BOTE_OK;
 }
 
+// test entry, not part of the ABI: the list merges over caller-supplied record
+// slots (tests/test_gpu_merge.py).  src: n_lists x n_obj x KP records (key,
+// rank), list i of objective o at record (i * n_obj + o) * KP, every slot the
+// caller's (what follows a terminator too); alt: the same for alt_lists lists,
+// or null with 0; kbound: n_obj keys or null; sel: one word or null (the
+// device reads alt and counters_alt when *sel > cap); counters, counters_alt:
+// two words each.  mode 0: merge_lists, a sweep's merge chain (one wide launch
+// when kbound && sel and both counts <= WIDE_MERGE_LISTS, else the tree down
+// to one list, and the counters); 1: launch_merge_wide; 2: one launch_merge
+// level with `out_stride` records between its output lists.  out: the result
+// lists, all KP slots of every objective (modes 0 and 1: one list; mode 2:
+// ceil(max(n_lists, alt_lists) / 8) lists, packed n_obj x KP apart);
+// out_counters: the result's two counters (mode 2 writes none).  The device
+// result is preset to bytes of 0xAB: a slot no kernel wrote shows as that.
+int bote_test_merge(int device, int mode, const uint64_t* src, uint32_t n_lists, const uint64_t* alt,
+                    uint32_t alt_lists, uint32_t n_obj, uint32_t K, const uint64_t* kbound, const uint64_t* sel,
+                    uint64_t cap, const uint64_t* counters, const uint64_t* counters_alt, uint64_t out_stride,
+                    uint64_t* out, uint64_t* out_counters) {
+  using bote::Rec;
+  DevGuard dev_guard;  // the caller's current device is restored on return
+  constexpr uint32_t TREE_LISTS_MAX = 1u << 16;
+  if (!src || !counters || !out || !out_counters || n_lists == 0) return fail(BOTE_E_ARG, "bad merge test arguments");
+  if ((alt != nullptr) != (alt_lists != 0)) return fail(BOTE_E_ARG, "alt and alt_lists go together");
+  if (sel && (!alt || !counters_alt)) return fail(BOTE_E_ARG, "sel needs alt and counters_alt");
+  if (mode < 0 || mode > 2) return fail(BOTE_E_ARG, "merge test mode is 0 (chain), 1 (wide) or 2 (one tree level)");
+  if (n_obj == 0 || n_obj > (uint32_t)bote::MAXOBJ) return fail(BOTE_E_RANGE, "1 to 8 objectives per merge");
+  if (K == 0 || K > (uint32_t)bote::KP) return fail(BOTE_E_RANGE, "K is 1 to KP");
+  if (n_lists > TREE_LISTS_MAX || alt_lists > TREE_LISTS_MAX) return fail(BOTE_E_RANGE, "at most 65536 lists");
+  if (mode == 1 && (n_lists > bote::WIDE_MERGE_LISTS || alt_lists > bote::WIDE_MERGE_LISTS))
+    return fail(BOTE_E_RANGE, "at most 4096 lists in one wide merge");
+  const uint64_t lstride = (uint64_t)n_obj * bote::KP;
+  if (mode == 2 && (out_stride < lstride || out_stride > 4 * lstride))
+    return fail(BOTE_E_RANGE, "out_stride is 1 to 4 list strides");
+  HIP_TRY(hipSetDevice(device));
+  const uint32_t groups = (std::max(n_lists, alt_lists) + bote::G_MERGE_LISTS - 1) / bote::G_MERGE_LISTS;
+  const size_t list_bytes = (size_t)lstride * 16, tmp_bytes = (size_t)groups * list_bytes;
+  const size_t res_bytes = mode == 2 ? (size_t)groups * out_stride * 16 : list_bytes + 16;
+  DBuf dsrc, dalt, dkb, dsel, dc, dca, tmp0, tmp1, res;
+  if (dsrc.alloc(n_lists * list_bytes) != hipSuccess || dalt.alloc(alt_lists * list_bytes) != hipSuccess ||
+      dkb.alloc(bote::MAXOBJ * 8) != hipSuccess || dsel.alloc(8) != hipSuccess || dc.alloc(16) != hipSuccess ||
+      dca.alloc(16) != hipSuccess || tmp0.alloc(tmp_bytes) != hipSuccess || tmp1.alloc(tmp_bytes) != hipSuccess ||
+      res.alloc(res_bytes) != hipSuccess)
+    return fail(BOTE_E_NOMEM, "hipMalloc merge test buffers");
+  HIP_TRY(hipMemcpy(dsrc.p, src, n_lists * list_bytes, hipMemcpyHostToDevice));
+  if (alt) HIP_TRY(hipMemcpy(dalt.p, alt, alt_lists * list_bytes, hipMemcpyHostToDevice));
+  if (kbound) HIP_TRY(hipMemcpy(dkb.p, kbound, (size_t)n_obj * 8, hipMemcpyHostToDevice));
+  if (sel) HIP_TRY(hipMemcpy(dsel.p, sel, 8, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(dc.p, counters, 16, hipMemcpyHostToDevice));
+  if (counters_alt) HIP_TRY(hipMemcpy(dca.p, counters_alt, 16, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemset(tmp0.p, 0xAB, tmp_bytes));
+  HIP_TRY(hipMemset(tmp1.p, 0xAB, tmp_bytes));
+  HIP_TRY(hipMemset(res.p, 0xAB, res_bytes));
+  const Rec* a = alt ? dalt.as<Rec>() : nullptr;
+  const unsigned long long* kb = kbound ? dkb.as<unsigned long long>() : nullptr;
+  const unsigned long long* sl = sel ? dsel.as<unsigned long long>() : nullptr;
+  const unsigned long long* ca = counters_alt ? dca.as<unsigned long long>() : nullptr;
+  uint64_t* cdst = (uint64_t*)((char*)res.p + list_bytes);
+  if (mode == 0) {
+    int rc = merge_lists(dsrc.as<Rec>(), n_lists, a, alt_lists, lstride, sl, cap, kb, tmp0.as<Rec>(), tmp1.as<Rec>(),
+                         res.p, n_obj, K, dc.as<unsigned long long>(), ca, nullptr);
+    if (rc) return rc;
+  } else if (mode == 1) {
+    HIP_TRY(bote::launch_merge_wide(dsrc.as<Rec>(), n_lists, a, alt_lists, lstride, sl, cap, kb, res.as<Rec>(), n_obj, K,
+                                    dc.as<unsigned long long>(), ca, cdst, nullptr));
+  } else {
+    HIP_TRY(bote::launch_merge(dsrc.as<Rec>(), n_lists, a, alt_lists, lstride, sl, cap, res.as<Rec>(), out_stride,
+                               n_obj, nullptr));
+  }
+  HIP_TRY(hipDeviceSynchronize());
+  if (mode == 2) {
+    HIP_TRY(hipMemcpy2D(out, list_bytes, res.p, (size_t)out_stride * 16, list_bytes, groups, hipMemcpyDeviceToHost));
+  } else {
+    HIP_TRY(hipMemcpy(out, res.p, list_bytes, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_counters, cdst, 16, hipMemcpyDeviceToHost));
+  }
+  return BOTE_OK;
+}
+
 }  // extern "C"

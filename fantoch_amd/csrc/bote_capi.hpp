@@ -234,5 +234,14 @@ namespace capi __attribute__((visibility("hidden"))) {
 int sweep_chunks(bote_sweep* s, uint64_t rb, uint64_t re, hipStream_t st, const Chunks** out);
 void unpack_result(const bote_sweep* s, const std::vector<uint8_t>& blk, bote_topk_record* out, uint32_t* out_count,
                    uint64_t* out_valid, uint64_t* out_digest);
+// bote_capi_sweep.hip: a launch's merge chain over raw device buffers (the
+// sweep's own, or bote_test_merge's): `lists` lists of `src`, or on the device
+// `alt_lists` of `alt` when sel && *sel > cap, into `result` (n_obj x KP
+// records, then the chosen counter pair at record lstride); tmp0 / tmp1 hold
+// ceil(max(lists, alt_lists) / 8) lists each (the merge tree's levels)
+int merge_lists(const Rec* src, uint32_t lists, const Rec* alt, uint32_t alt_lists, uint64_t lstride,
+                const unsigned long long* sel, uint64_t cap, const unsigned long long* kbound, Rec* tmp0, Rec* tmp1,
+                void* result, uint32_t n_obj, uint32_t K, const unsigned long long* counters,
+                const unsigned long long* counters_alt, hipStream_t st);
 }  // namespace capi
 }  // namespace bote

@@ -549,57 +549,65 @@ void bote::capi::unpack_result(const bote_sweep* s, const std::vector<uint8_t>& 
   bote::host::unpack_result(blk.data(), s->n_obj, s->K, bote::KP, (TopkRecord*)out, out_count, out_valid, out_digest);
 }
 
-extern "C" {
-
-// Merge `lists` per-block lists into the result block and append the counters:
-// one launch when the group kernel bounded its lists (kbound: few records per
-// list), else the tree of 8-way merges (full lists).
+// Merge `lists` lists of `src` (list i of objective o at src[i * lstride + o *
+// KP]) into the result block (n_obj x KP records, then the two counters at
+// record lstride): one launch when the group kernel bounded its lists (kbound:
+// few records per list), else the tree of 8-way merges (full lists) through
+// tmp0 / tmp1 (ceil(max(lists, alt_lists) / 8) lists each).
 // With `sel` (fast path), the first level reads the overflow fallback's
-// `alt_lists` lists and counters instead when *sel > QUEUE_CAP (on the device).
+// `alt_lists` lists and counters instead when *sel > cap (on the device).
 static bool wide_merge(uint32_t lists, uint32_t alt_lists) {
   return lists <= bote::WIDE_MERGE_LISTS && alt_lists <= bote::WIDE_MERGE_LISTS;
 }
-static int merge_chain(bote_sweep* s, uint32_t lists, hipStream_t st, const unsigned long long* sel = nullptr,
-                       uint32_t alt_lists = 0, const unsigned long long* kbound = nullptr) {
-  const uint64_t lstride = (uint64_t)s->n_obj * bote::KP;
-  Rec* rec_out = s->result.as<Rec>();
-  uint64_t* cdst = (uint64_t*)((char*)s->result.p + lstride * 16);
-  if (s->n_obj && kbound && sel && wide_merge(lists, alt_lists)) {
+int bote::capi::merge_lists(const Rec* src, uint32_t lists, const Rec* alt, uint32_t alt_lists, uint64_t lstride,
+                            const unsigned long long* sel, uint64_t cap, const unsigned long long* kbound, Rec* tmp0,
+                            Rec* tmp1, void* result, uint32_t n_obj, uint32_t K, const unsigned long long* counters,
+                            const unsigned long long* counters_alt, hipStream_t st) {
+  Rec* rec_out = (Rec*)result;
+  uint64_t* cdst = (uint64_t*)((char*)result + lstride * 16);
+  if (n_obj && kbound && sel && wide_merge(lists, alt_lists)) {
     // one launch: the lists' filled prefixes gathered and ranked in LDS, and
     // the counters picked by the same device choice
-    HIP_TRY(bote::launch_merge_wide(s->top.as<Rec>(), lists, s->top_alt.as<Rec>(), alt_lists, lstride, sel, QUEUE_CAP,
-                                    kbound, rec_out, s->n_obj, s->K, s->counters.as<unsigned long long>(),
-                                    s->counters_alt.as<unsigned long long>(), cdst, st));
+    HIP_TRY(bote::launch_merge_wide(src, lists, alt, alt_lists, lstride, sel, cap, kbound, rec_out, n_obj, K, counters,
+                                    counters_alt, cdst, st));
     return BOTE_OK;
   }
-  if (s->n_obj) {
-    const Rec* src = s->top.as<Rec>();
-    Rec* bufs[2] = {s->tmp0.as<Rec>(), s->tmp1.as<Rec>()};
+  if (n_obj) {
+    Rec* bufs[2] = {tmp0, tmp1};
     int b = 0;
     if (sel) {
       Rec* dst = lists > bote::G_MERGE_LISTS || alt_lists > bote::G_MERGE_LISTS ? bufs[b] : rec_out;
-      HIP_TRY(bote::launch_merge(src, lists, s->top_alt.as<Rec>(), alt_lists, lstride, sel, QUEUE_CAP, dst, lstride,
-                                 s->n_obj, st));
+      HIP_TRY(bote::launch_merge(src, lists, alt, alt_lists, lstride, sel, cap, dst, lstride, n_obj, st));
       lists = (std::max(lists, alt_lists) + bote::G_MERGE_LISTS - 1) / bote::G_MERGE_LISTS;
       src = dst;
       b ^= 1;
       if (dst == rec_out) lists = 0;
     }
     while (lists > bote::G_MERGE_LISTS) {
-      HIP_TRY(bote::launch_merge(src, lists, nullptr, 0, lstride, nullptr, 0, bufs[b], lstride, s->n_obj, st));
+      HIP_TRY(bote::launch_merge(src, lists, nullptr, 0, lstride, nullptr, 0, bufs[b], lstride, n_obj, st));
       src = bufs[b];
       b ^= 1;
       lists = (lists + bote::G_MERGE_LISTS - 1) / bote::G_MERGE_LISTS;
     }
-    if (lists) HIP_TRY(bote::launch_merge(src, lists, nullptr, 0, lstride, nullptr, 0, rec_out, lstride, s->n_obj, st));
+    if (lists) HIP_TRY(bote::launch_merge(src, lists, nullptr, 0, lstride, nullptr, 0, rec_out, lstride, n_obj, st));
   }
   if (sel) {
-    HIP_TRY(bote::launch_pick_counters(s->counters.as<unsigned long long>(), s->counters_alt.as<unsigned long long>(),
-                                       sel, QUEUE_CAP, cdst, st));
+    HIP_TRY(bote::launch_pick_counters(counters, counters_alt, sel, cap, cdst, st));
   } else {
-    HIP_TRY(hipMemcpyAsync(cdst, s->counters.p, 16, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpyAsync(cdst, counters, 16, hipMemcpyDeviceToDevice, st));
   }
   return BOTE_OK;
+}
+
+extern "C" {
+
+// Merge `lists` per-block lists into the result block and append the counters
+// (merge_lists on the sweep's buffers).
+static int merge_chain(bote_sweep* s, uint32_t lists, hipStream_t st, const unsigned long long* sel = nullptr,
+                       uint32_t alt_lists = 0, const unsigned long long* kbound = nullptr) {
+  return merge_lists(s->top.as<Rec>(), lists, s->top_alt.as<Rec>(), alt_lists, (uint64_t)s->n_obj * bote::KP, sel,
+                     QUEUE_CAP, kbound, s->tmp0.as<Rec>(), s->tmp1.as<Rec>(), s->result.p, s->n_obj, s->K,
+                     s->counters.as<unsigned long long>(), s->counters_alt.as<unsigned long long>(), st);
 }
 
 static int timing_slot(bote_sweep* s, hipEvent_t*& e0, hipEvent_t*& e1) {

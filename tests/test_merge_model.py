@@ -12,8 +12,8 @@ This restates that procedure in plain Python with small sizes (ties in the
 keys, blocks that finish in any order, windows smaller than the gathered
 records) and checks it against the K least of all configs: the argument that
 no record of the union's top-K is dropped is the thing under test.  The HIP
-kernels themselves are checked on the GPU (tests/test_gpu_*.py, every
-fixture's top-K).
+kernels themselves are checked on the GPU against a sort, on lists built from
+the helpers here (tests/test_gpu_merge.py).
 
 Round 5 adds the heads' bound (BOTE_MERGE_HEADS): before counting, the merge
 tightens the bound to a key t with at least K head records (the first
