@@ -40,6 +40,7 @@ OBJ_MDTM = 18
 MDTM_SUM_BITS = 27
 FT_F1, FT_F1F2 = 1, 2
 KP = 128
+CENSUS_MAX_THRESHOLDS = 16  # BOTE_CENSUS_MAX_THRESHOLDS: thresholds per objective of a census launch
 
 
 def OBJ_PCTL(bp: int) -> int:
@@ -68,6 +69,8 @@ EXPORTS = [
     "bote_batch_create", "bote_batch_launch", "bote_batch_result", "bote_batch_deferred", "bote_batch_path",
     "bote_batch_last_kernel_ms", "bote_batch_plan", "bote_batch_destroy",
     "bote_batch_create_bounded", "bote_batch_limits", "bote_mean_decrease_limit",
+    "bote_census_create", "bote_census_launch", "bote_census_result", "bote_census_deferred", "bote_census_path",
+    "bote_census_last_kernel_ms", "bote_census_destroy",
 ]
 KERNELS = {None: 0, "auto": 0, "generic": 1, "fast": 2, "group": 3}
 
@@ -102,7 +105,7 @@ _LIB = None
 
 def build(jobs: int = 8) -> str:
     """Compile libbote_hip.so for gfx950 (hipcc cross-compiles without a GPU).
-    The generic kernel's five units are the long ones: 8 jobs let them overlap."""
+    The generic kernel's six units are the long ones: 8 jobs let them overlap."""
     subprocess.run(["make", "-s", "-C", CSRC, f"-j{jobs}"], check=True)
     return LIB_PATH
 
@@ -206,6 +209,15 @@ def lib():
         L.bote_batch_create_bounded.argtypes = L.bote_batch_create.argtypes[:-1] + [_u64p, C.POINTER(_vp)]
         L.bote_batch_limits.argtypes = [_vp, _u32p]
         L.bote_mean_decrease_limit.argtypes = [C.c_uint64, C.c_uint32, C.c_double, C.POINTER(C.c_uint32)]
+    if hasattr(L, "bote_census_create"):  # (the same)
+        L.bote_census_create.argtypes = [_vp, _u32p, C.c_uint32, _u32p, C.c_uint32, C.c_uint32, C.POINTER(Objective),
+                                         C.c_uint32, C.POINTER(RankingParamsC), C.c_int, C.POINTER(_vp)]
+        L.bote_census_launch.argtypes = [_vp, _vp, C.c_uint32, C.c_uint64, C.c_uint64, _vp]
+        L.bote_census_result.argtypes = [_vp, _vp, _vp, C.POINTER(C.c_uint64)]
+        L.bote_census_deferred.argtypes = [_vp, _vp, C.POINTER(C.c_uint64)]
+        L.bote_census_path.argtypes = [_vp, C.POINTER(C.c_int)]
+        L.bote_census_last_kernel_ms.argtypes = [_vp, C.POINTER(C.c_float)]
+        L.bote_census_destroy.argtypes = [_vp]
     if hasattr(L, "bote_percentile_index"):  # (absent from an older BOTE_LIB_PATH build loaded for A/B timing)
         L.bote_percentile_index.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_int)]
     _LIB = L

@@ -15,6 +15,7 @@ import itertools
 import math
 import os
 from dataclasses import dataclass
+from fractions import Fraction
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -1037,6 +1038,143 @@ class PinnedBatch:
     def config_of(self, rank: int) -> List[int]:
         pos = _lib.colex_unrank(rank, self.n, len(self.servers))
         return [int(self.servers[p]) for p in pos]
+
+
+@dataclass
+class CensusResult:
+    below: np.ndarray  # [n_obj, T] uint64: the offered configs before each threshold
+    valid: int         # configs with a valid compute_score (only with a SCORE objective)
+
+
+class Census:
+    """Where configurations stand among all C(ns, n) (bote_census_*): counts of the
+    configs ranked before given (key, rank) records, per objective, in the lists'
+    unsigned (key, rank) order.  A SCORE objective ranks the valid configs only,
+    every other kind ranks every config, so objective o's population is
+    `result().valid` for SCORE and the launched ranks otherwise.  Base key set.
+    Counts of disjoint rank ranges add."""
+
+    U64_MAX = (1 << 64) - 1
+
+    def __init__(self, dp: DevicePlanet, servers: Sequence[int], clients: Sequence[int], n: int,
+                 objectives=DEFAULT_OBJECTIVES, ranking: Optional[RankingParams] = None,
+                 kernel: Optional[str] = None):
+        ranking = DEFAULT_RANKING if ranking is None else ranking
+        self.dp, self.n, self.kernel = dp, n, kernel
+        self.servers, self.clients = u32(servers), u32(clients)
+        self.objectives = list(objectives)
+        self.ranking = ranking
+        self.T = 0
+        objs = (_lib.Objective * max(len(self.objectives), 1))(*[_lib.Objective(k, s) for k, s in self.objectives])
+        self.h = None
+        h = C.c_void_p()
+        check(lib().bote_census_create(dp.h, self.servers, len(self.servers), self.clients, len(self.clients), n,
+                                       objs, len(self.objectives), C.byref(_lib.ranking_params_c(ranking)),
+                                       _lib.KERNELS[kernel], C.byref(h)))
+        self.h = h
+        self.total = _lib.binomial(len(self.servers), n)
+
+    def __del__(self):
+        try:
+            if self.h:
+                lib().bote_census_destroy(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+    def launch(self, thresholds, rank_begin: int = 0, rank_end: Optional[int] = None, stream: Optional[int] = None):
+        """thresholds: per objective T (key, rank) records, ascending, 1 <= T <= 16, the same T
+        for every objective (an [n_obj, T, 2] array of u64, or nested sequences of Python ints)."""
+        no = len(self.objectives)
+        rows = [[(int(k), int(r)) for k, r in row] for row in thresholds]
+        if len(rows) != no or len({len(row) for row in rows}) > 1:
+            raise ValueError("one row of thresholds per objective, all of one length")
+        self.T = len(rows[0]) if rows else 1
+        thr = np.array(rows, dtype=np.uint64).reshape(no, self.T, 2)
+        thr = np.ascontiguousarray(thr)
+        re = self.total if rank_end is None else rank_end
+        check(lib().bote_census_launch(self.h, ptr(thr), self.T, rank_begin, re, C.c_void_p(stream) if stream else None))
+
+    def result(self, stream: Optional[int] = None) -> CensusResult:
+        below = np.zeros((len(self.objectives), self.T), np.uint64)
+        valid = C.c_uint64()
+        check(lib().bote_census_result(self.h, C.c_void_p(stream) if stream else None, ptr(below), C.byref(valid)))
+        return CensusResult(below, valid.value)
+
+    def deferred(self, stream: Optional[int] = None) -> int:
+        """Configs the last launch's fast kernel deferred to the exact generic kernel."""
+        v = C.c_uint64()
+        check(lib().bote_census_deferred(self.h, C.c_void_p(stream) if stream else None, C.byref(v)))
+        return v.value
+
+    def kernel_path(self) -> str:
+        v = C.c_int()
+        check(lib().bote_census_path(self.h, C.byref(v)))
+        return ("generic", "fast")[v.value]
+
+    def kernel_ms(self) -> float:
+        v = C.c_float()
+        check(lib().bote_census_last_kernel_ms(self.h, C.byref(v)))
+        return v.value
+
+    def population(self, valid: int) -> List[int]:
+        """Per objective, the configs a whole-range launch ranks: `valid` for SCORE, every config otherwise."""
+        return [valid if k == _lib.OBJ_SCORE else self.total for k, _ in self.objectives]
+
+    def position_of(self, config_positions: Sequence[int]) -> List[Tuple[Optional[int], int]]:
+        """Per objective (position, population) of the config with these positions into
+        `servers`: its 0-based index in the objective's full ordering (None for a SCORE
+        objective when the config is not valid).  The config's records are the device's
+        own: a K = 1 sweep over its single rank."""
+        pos = sorted(int(p) for p in config_positions)
+        if len(pos) != self.n or len(set(pos)) != self.n or not all(0 <= p < len(self.servers) for p in pos):
+            raise ValueError(f"a config is {self.n} distinct positions into the {len(self.servers)} servers")
+        rank = sum(math.comb(p, j + 1) for j, p in enumerate(pos))
+        one = Sweep(self.dp, self.servers, self.clients, self.n, self.objectives, K=1, ranking=self.ranking)
+        one.launch(rank, rank + 1)
+        tops = one.result().tops
+        self.launch([[t[0] if t else (0, 0)] for t in tops])
+        res = self.result()
+        pops = self.population(res.valid)
+        return [(int(res.below[o, 0]) if tops[o] else None, pops[o]) for o in range(len(self.objectives))]
+
+    def quantiles(self, qs: Sequence[float]) -> List[List[Optional[int]]]:
+        """Per objective and q in (0, 1], the key of the record at 0-based index
+        ceil(q * population) - 1 of the objective's full ordering (None: nothing is
+        ranked).  Exact: the least key k with below((k + 1, 0)) >= ceil(q * population),
+        found by a 17-ary search on the u64 keys, 16 thresholds (key, 0) per launch, at
+        most 16 launches per q, all objectives in the same launches."""
+        no = len(self.objectives)
+        for q in qs:
+            if not 0.0 < float(q) <= 1.0:
+                raise ValueError(f"quantile {q} is outside (0, 1]")
+        T = _lib.CENSUS_MAX_THRESHOLDS
+        self.launch([[(0, 0)]] * no)  # the populations (the valid count)
+        pops = self.population(self.result().valid)
+        out: List[List[Optional[int]]] = [[] for _ in range(no)]
+        for q in qs:
+            # Fraction: q * population exactly (a float product could round across an integer)
+            want = [max(1, math.ceil(Fraction(float(q)) * p)) if p else 0 for p in pops]
+            # the answer of objective o lies in [lo[o], hi[o]]: below((hi + 1, 0)) >= want, and
+            # for hi = 2^64 - 1 every ranked config has a key at or below it
+            lo, hi = [0] * no, [self.U64_MAX] * no
+            while any(want[o] and lo[o] < hi[o] for o in range(no)):
+                probes = [[lo[o] + (hi[o] - lo[o]) * i // (T + 1) for i in range(1, T + 1)]
+                          if want[o] and lo[o] < hi[o] else [0] * T for o in range(no)]
+                # (a probe is at most hi - 1 <= 2^64 - 2: its successor is a key)
+                self.launch([[(k + 1 if want[o] and lo[o] < hi[o] else 0, 0) for k in probes[o]] for o in range(no)])
+                below = self.result().below
+                for o in range(no):
+                    if not want[o] or lo[o] >= hi[o]:
+                        continue
+                    for i, k in enumerate(probes[o]):
+                        if int(below[o, i]) >= want[o]:
+                            hi[o] = k
+                            break
+                        lo[o] = k + 1
+            for o in range(no):
+                out[o].append(hi[o] if want[o] else None)
+        return out
 
 
 class MultiDeviceSearch:

@@ -24,6 +24,9 @@ main.rs:31-60).  Subcommands expose them, and the sweep the hot path serves:
   python -m fantoch_amd evolve (--synthetic R [--seed S] | --lat-dir D [--input R13C13|R17C17|R20C20])
                         [--min-n 3] [--max-n 13] [--beam B] [-K 100] [--ranking 110,35,0,15] [--ft F1F2]
                         [--chains 1]
+  python -m fantoch_amd census (--synthetic R [--seed S] | --lat-dir D) --n N [--objectives ...]
+                        [--ranking 110,35,0,15] [--ft F1F2] [--kernel auto|generic|fast]
+                        [--config a,b,c] [--quantiles 0.01,0.5,0.99]
 """
 from __future__ import annotations
 
@@ -269,6 +272,75 @@ def sweep(args, out=sys.stdout):
     return block(res, pinned)
 
 
+def _decode_key(kind: int, slot: int, key: int, n: int, clients: int) -> dict:
+    """A quantile's key in the objective's own terms (the keys of include/bote_hip.h)."""
+    import numpy as np
+
+    from . import _lib
+    from .bote import max_key, mdtm_key, pctl_key
+    from .evolve import key_score
+
+    rec = {"key": str(key)}
+    count = n if 5 <= slot < 10 else clients
+    if kind == _lib.OBJ_SCORE:
+        rec["score"] = float(key_score(np.array([key], np.uint64))[0])
+    elif kind == _lib.OBJ_MEAN:
+        rec["sum"], rec["mean"] = key, key / count
+    elif kind == _lib.OBJ_COV:  # the key is fl64(V / S1^2) = cov^2 (count - 1) / count
+        ratio = float(np.array([key], np.uint64).view(np.float64)[0])
+        rec["cov"] = None if ratio != ratio or count < 2 else (ratio * count / (count - 1)) ** 0.5
+    elif kind == _lib.OBJ_MAX:
+        rec["max"], rec["sum"] = max_key(key)
+    elif _lib.is_pctl(kind):
+        twice, rec["sum"] = pctl_key(key)
+        rec["percentile"] = twice / 2
+    elif kind == _lib.OBJ_MDTM:
+        h, rec["sum"] = mdtm_key(key)
+        rec["mdtm"] = 2 * h / count ** 2
+    return rec
+
+
+def census(args, out=sys.stdout):
+    """Where a config stands among all C(R, n) (--config: per objective its position,
+    the population and their ratio) and the shape of each objective over the space
+    (--quantiles: per objective the key at each quantile of the full ordering), by
+    census sweeps (bote_census_*), as one JSON line."""
+    import numpy as np
+
+    from . import _lib
+    from .bote import Census, DevicePlanet, FTMetric, RankingParams
+
+    if not args.config and not args.quantiles:
+        raise ValueError("census: give --config and/or --quantiles")
+    planet = _planet(args)
+    srv = np.arange(planet.R, dtype=np.uint32)
+    objs = _objectives(args.objectives)
+    a, b, c, d = (float(x) for x in args.ranking.split(","))
+    params = RankingParams(a, b, c, d, args.n, args.n, FTMetric[args.ft])
+    cs = Census(DevicePlanet(planet, args.device), srv, srv, args.n, objs, ranking=params,
+                kernel=None if args.kernel == "auto" else args.kernel)
+    names = [_objective_name(k) + ("" if k == _lib.OBJ_SCORE else ":" + _lib.SLOT_NAMES_X[s]) for k, s in objs]
+    doc = {"regions": planet.R, "n": args.n, "configs": cs.total, "kernel": cs.kernel_path(),
+           "objectives": [{"objective": name} for name in names]}
+    if args.config:
+        try:
+            pos = _pinned(args.config, planet.names)
+        except ValueError as e:  # (the same syntax as --pinned: names or positions)
+            raise ValueError(str(e).replace("--pinned", "--config")) from None
+        doc["config"] = [planet.names[p] for p in sorted(pos)]
+        for o, (position, population) in enumerate(cs.position_of(pos)):
+            doc["objectives"][o].update(position=position, population=population,
+                                        share=None if position is None or not population else position / population)
+    if args.quantiles:
+        qs = [float(x) for x in args.quantiles.split(",")]
+        doc["quantiles"] = qs
+        for o, keys in enumerate(cs.quantiles(qs)):
+            doc["objectives"][o]["quantile_keys"] = [None if k is None else _decode_key(*objs[o], k, args.n, planet.R)
+                                                     for k in keys]
+    print(json.dumps(doc), file=out)
+    return doc
+
+
 def evolve(args, out=sys.stdout) -> int:
     """The streaming evolving search (evolve.py): the best chains' scores and, per
     level, the region names, then whether the search was exhaustive (then the
@@ -367,6 +439,18 @@ def build_parser() -> argparse.ArgumentParser:
                         "min_mean_decrease")
     p.add_argument("--ft", default="F1F2", choices=["F1", "F1F2"])
     p.add_argument("--chains", type=int, default=1, help="best chains to print")
+    p = sub.add_parser("census", allow_abbrev=False,
+                       help="census sweeps: a config's position among all C(R, n), quantiles of the objectives")
+    planet_flags(p, synthetic=True)
+    p.add_argument("--n", type=int, required=True)
+    p.add_argument("--objectives", default="default")
+    p.add_argument("--ranking", default="110,35,0,15",
+                   help="min_mean_fpaxos_improv,min_mean_epaxos_improv,min_fairness_fpaxos_improv,"
+                        "min_mean_decrease")
+    p.add_argument("--ft", default="F1F2", choices=["F1", "F1F2"])
+    p.add_argument("--kernel", default="auto", choices=["auto", "generic", "fast"])
+    p.add_argument("--config", default=None, help="region names or positions: the config whose position is asked")
+    p.add_argument("--quantiles", default=None, help="comma-separated q in (0, 1]: the key at each quantile")
     return ap
 
 
@@ -383,6 +467,8 @@ def main(argv: Optional[Sequence[str]] = None, out=sys.stdout) -> int:
         config_stats(args, out)
     elif cmd == "sweep":
         sweep(args, out)
+    elif cmd == "census":
+        census(args, out)
     elif cmd == "evolve":
         return evolve(args, out)
     return 0

@@ -29,6 +29,7 @@
 #include "bote_kernels.hpp"
 #include <type_traits>
 
+#include "bote_census.hpp"
 #include "bote_pinned.hpp"
 
 namespace bote {
@@ -69,10 +70,11 @@ __host__ __device__ inline size_t smem_layout(const EvalArgs& a, int N, int NLW,
   return o;
 }
 
-template <int N>
+// (TOPK: laid out with the top-K structures whatever a.out_top says: the census variant)
+template <int N, bool TOPK = false>
 __device__ inline Smem carve(const EvalArgs& a, unsigned char* base, int NLW) {
   size_t off[12];
-  smem_layout(a, N, NLW, blockDim.x, a.out_top != nullptr, off);
+  smem_layout(a, N, NLW, blockDim.x, TOPK || a.out_top != nullptr, off);
   Smem s;
   s.mat = (uint32_t*)(base + off[0]);
   s.clioff = (uint32_t*)(base + off[1]);
@@ -840,31 +842,50 @@ __device__ __forceinline__ void write_full(const EvalArgs& a, uint64_t oi, const
   if (a.out_valid) a.out_valid[oi] = r.valid ? 1 : 0;
 }
 
+// the census variant's sink in the top-K regions it takes (eval_kernel below)
+__device__ __forceinline__ CensusLds census_lds(const Smem& s) {
+  return CensusLds{s.tk.top, (unsigned long long*)s.tk.cand};
+}
+
 // ------------------------------------------------------------ the kernel --
 // PIN: the pinned variant (bote_pinned.hpp; top-K sweeps of the base key set in
 // the rank-range mode); the digest and the records carry the full colex rank.
-template <int N, bool FULL, bool X, int PASSES = EVAL_PLAIN, bool PIN = false>
-__global__ void __launch_bounds__(256) eval_kernel(std::conditional_t<PIN, PinEvalArgs, EvalArgs> a) {
+// CENSUS: the census variant (bote_census.hpp; base key set, ranks or the
+// deferred rank list): the objectives' keys as a top-K sweep builds them, and
+// census_step in place of topk_step.  It is laid out as a top-K sweep (the
+// launcher sizes it so): the thresholds take the lists' region (tk.top, at
+// least n_obj x KP records), the bins the candidate buffer's (tk.cand, 16 B per
+// thread of the block).
+template <int N, bool FULL, bool X, int PASSES = EVAL_PLAIN, bool PIN = false, bool CENSUS = false>
+__global__ void __launch_bounds__(256)
+    eval_kernel(std::conditional_t<CENSUS, CensusEvalArgs, std::conditional_t<PIN, PinEvalArgs, EvalArgs>> a) {
   static_assert(!PIN || (!FULL && !X), "the pinned variant is a top-K sweep of the base key set");
+  static_assert(!CENSUS || (!FULL && !X && !PIN), "the census variant sweeps ranks of the base key set");
+  static_assert(CENSUS_T <= KP && CENSUS_T * 8 * MAXOBJ <= 256 * 16, "the census sink fits the top-K regions it takes");
   constexpr bool PCTL = PASSES >= EVAL_PCTL;
   static_assert(!(FULL && PCTL), "percentile and MDTM objectives belong to top-K sweeps");
   constexpr int NS = CfgOut<N, X>::NS;
   using Cursor = ConfigCursor<N, PIN>;
   extern __shared__ __align__(16) unsigned char smem[];
   if (a.run_if_over && *a.run_if_over <= a.over_cap) return;  // block-uniform, before any barrier
-  const Smem s = carve<N>(a, smem, QPhase<N, X>::NLW);
+  const Smem s = carve<N, CENSUS>(a, smem, QPhase<N, X>::NLW);
   const uint32_t BD = blockDim.x, tid = threadIdx.x;
-  const bool topk = !FULL && a.out_top != nullptr;
+  const bool topk = CENSUS || (!FULL && a.out_top != nullptr);
+  if constexpr (CENSUS) {
+    // a fix-up over a queue that overflowed: the fallback counts the whole range (block-uniform)
+    if (a.rank_list && *a.rank_count > a.re - a.rb) return;
+  }
   if (a.rank_list && *a.rank_count == 0) {
     // the deferred-config fix-up with nothing deferred (the common case):
     // empty lists for the merge, nothing staged (block-uniform)
-    if (topk) {
+    if (topk && !CENSUS) {
       Rec* dst = a.out_top + (size_t)blockIdx.x * a.n_obj * KP;
       for (uint32_t i = tid; i < (uint32_t)a.n_obj * KP; i += BD) dst[i] = rec_max();
     }
     return;
   }
-  stage_planet<N>(a, s, Cursor::unranks(a), topk);
+  if constexpr (CENSUS) census_init(census_lds(s), nullptr, a.cz, a.n_obj, a.obj_kind);  // (published by the stage's barriers)
+  stage_planet<N>(a, s, Cursor::unranks(a), topk && !CENSUS);
 
   const uint64_t total = Cursor::total(a), runlen = Cursor::runlen(a);
   const uint64_t njobs = (total + runlen - 1) / runlen;
@@ -929,7 +950,8 @@ __global__ void __launch_bounds__(256) eval_kernel(std::conditional_t<PIN, PinEv
             }
           }
         }
-        topk_step(s.tk, a.n_obj, a.K, key, ok, frank);
+        if constexpr (CENSUS) census_step(census_lds(s), a.n_obj, a.cz.T, key, ok, frank);
+        else topk_step(s.tk, a.n_obj, a.K, key, ok, frank);
       }
       Cursor::next(a, have, p, q, rank);
     }
@@ -939,7 +961,10 @@ __global__ void __launch_bounds__(256) eval_kernel(std::conditional_t<PIN, PinEv
     if (valid_cnt) atomicAdd(&a.out_counters[0], (unsigned long long)valid_cnt);
     if (digest) atomicAdd(&a.out_counters[1], (unsigned long long)digest);
   }
-  if (topk) {
+  if constexpr (CENSUS) {
+    __syncthreads();
+    census_flush(census_lds(s), a.cz, a.n_obj);
+  } else if (topk) {
     __syncthreads();
     Rec* dst = a.out_top + (size_t)blockIdx.x * a.n_obj * KP;
     for (uint32_t i = tid; i < (uint32_t)a.n_obj * KP; i += BD) dst[i] = s.tk.top[i];
@@ -959,5 +984,6 @@ BOTE_HIDDEN const void* eval_fn_topk(uint32_t n, bool keys);    // bote_eval_top
 BOTE_HIDDEN const void* eval_fn_pctl(uint32_t n, bool keys);    // bote_eval_pctl.hip: top-K, EVAL_PCTL
 BOTE_HIDDEN const void* eval_fn_mdtm(uint32_t n, bool keys);    // bote_eval_mdtm.hip: top-K, EVAL_MDTM
 BOTE_HIDDEN const void* eval_fn_pinned(uint32_t n, bool passes);  // bote_eval_pinned.hip: EVAL_MDTM (passes) or EVAL_PLAIN
+BOTE_HIDDEN const void* eval_fn_census(uint32_t n, bool passes);  // bote_eval_census.hip: the same two, census sink
 
 }  // namespace bote

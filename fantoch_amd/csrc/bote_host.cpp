@@ -803,6 +803,43 @@ Status check_rank_span_total(uint64_t total, uint64_t rank_begin, uint64_t rank_
   return OK;
 }
 
+Status check_census_args(uint32_t R, const uint32_t* servers, uint32_t ns, const uint32_t* clients, uint32_t nc,
+                         uint32_t n, const bote_objective* objs, uint32_t n_obj, const bote_ranking_params* rp,
+                         int kernel, bool& has_score) {
+  has_score = false;
+  if (kernel == BOTE_KERNEL_GROUP)
+    return fail(BOTE_E_ARG, "the group kernel does not run census sweeps (fast or generic kernel)");
+  return check_sweep_args(R, servers, ns, clients, nc, n, objs, n_obj, 1, rp, kernel, 0, has_score);
+}
+
+Status census_route(bool eligible, const bote_objective* objs, uint32_t n_obj, int kernel, int& path) {
+  bool plain = true;  // SCORE, MEAN and COV objectives only
+  for (uint32_t o = 0; o < n_obj; ++o) plain = plain && objs[o].kind <= BOTE_OBJ_COV;
+  path = 0;
+  if (kernel == BOTE_KERNEL_GENERIC) return OK;
+  if (kernel == BOTE_KERNEL_FAST) {
+    if (!plain)
+      return fail(BOTE_E_ARG, "the fast kernel's census variant computes SCORE, MEAN and COV objectives (generic kernel)");
+    if (!eligible) return fail(BOTE_E_ARG, "the fast/group kernel is not eligible for this planet and lists");
+  }
+  path = plain && eligible ? 1 : 0;
+  return OK;
+}
+
+Status check_census_launch(const TopkRecord* thr, uint32_t n_obj, uint32_t T, uint32_t ns, uint32_t n,
+                           uint64_t rank_begin, uint64_t rank_end) {
+  if (T == 0 || T > CENSUS_MAX_THRESHOLDS)
+    return fail(BOTE_E_ARG, "a census launch takes 1 to " + std::to_string(CENSUS_MAX_THRESHOLDS) + " thresholds per objective");
+  if (n_obj && !thr) return fail(BOTE_E_ARG, "thresholds null");
+  for (uint32_t o = 0; o < n_obj; ++o)
+    for (uint32_t t = 1; t < T; ++t) {
+      const TopkRecord &a = thr[(size_t)o * T + t - 1], &b = thr[(size_t)o * T + t];
+      if (b.key < a.key || (b.key == a.key && b.rank < a.rank))
+        return fail(BOTE_E_ARG, "objective " + std::to_string(o) + ": thresholds must ascend in (key, rank)");
+    }
+  return check_rank_span(ns, n, rank_begin, rank_end);
+}
+
 Status check_chain_levels(uint32_t ns, const uint32_t* counts, const uint64_t* const* masks,
                           const double* const* scores, const double* const* means) {
   for (int l = 0; l < 6; ++l) {

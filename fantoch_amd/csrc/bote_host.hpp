@@ -322,6 +322,29 @@ Status check_mean_limit_args(uint64_t prev_s1, uint32_t count, const uint32_t* o
 Status check_bounded_args(const uint64_t* prev_s1, uint32_t n_sets, uint32_t nc, const bote_ranking_params* rp);
 // rank_begin <= rank_end <= `total` (a pinned sweep's pinned_total).
 Status check_rank_span_total(uint64_t total, uint64_t rank_begin, uint64_t rank_end);
+// ------------------------------------------------------- census sweeps --
+// (DESIGN.md §4 "Census sweeps": counts of the configs ranked before given records)
+constexpr uint32_t CENSUS_MAX_THRESHOLDS = BOTE_CENSUS_MAX_THRESHOLDS;
+// bote_census_create.  In order: a forced group kernel (it is not touched by
+// censuses), then check_sweep_args with K = 1 on the base key set.
+Status check_census_args(uint32_t R, const uint32_t* servers, uint32_t ns, const uint32_t* clients, uint32_t nc,
+                         uint32_t n, const bote_objective* objs, uint32_t n_obj, const bote_ranking_params* rp,
+                         int kernel, bool& has_score);
+// The kernel a census runs (path: 0 generic, 1 fast), as pinned sweeps are
+// routed.  `eligible`: fast_eligible's verdict on the planet and lists.  AUTO
+// and a forced fast kernel run the fast kernel's census variant on an eligible
+// planet with only SCORE, MEAN and COV objectives; a MAX, percentile or MDTM
+// objective, an ineligible planet and a forced generic kernel run the generic
+// kernel's; a forced fast kernel with such an objective, or on an ineligible
+// planet, is BOTE_E_ARG.
+Status census_route(bool eligible, const bote_objective* objs, uint32_t n_obj, int kernel, int& path);
+// bote_census_launch.  In order: T outside 1 .. CENSUS_MAX_THRESHOLDS, a null
+// list, then per objective, lowest index first, a threshold below its
+// predecessor in the unsigned (key, rank) order (equal neighbours pass; any u64
+// is a legal key), then the rank span.
+Status check_census_launch(const TopkRecord* thr, uint32_t n_obj, uint32_t T, uint32_t ns, uint32_t n,
+                           uint64_t rank_begin, uint64_t rank_end);
+
 // bote_evolving_chains' six levels (n = 3, 5, .., 13): arrays present where a
 // level has entries, every mask an n-subset of the ns servers.
 Status check_chain_levels(uint32_t ns, const uint32_t* counts, const uint64_t* const* masks,

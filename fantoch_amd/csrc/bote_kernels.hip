@@ -125,7 +125,10 @@ size_t eval_smem_bytes(const EvalArgs& a, uint32_t n, uint32_t bd, bool topk) {
 // `pin`: the pinned variant (bote_pinned.hpp; top-K, base keys): EVAL_PLAIN, or
 // EVAL_MDTM for a sweep with a percentile or an MDTM objective (each level has
 // the passes of the ones below it)
-static const void* eval_fn(uint32_t n, bool full, bool keys, int passes, bool pin) {
+// `census`: the census variant (bote_census.hpp; base keys, unpinned): EVAL_PLAIN,
+// or EVAL_MDTM for a census with a MAX, percentile or MDTM objective
+static const void* eval_fn(uint32_t n, bool full, bool keys, int passes, bool pin, bool census = false) {
+  if (census) return full || keys || pin ? nullptr : eval_fn_census(n, passes != EVAL_PLAIN);
   if (pin) return full || keys ? nullptr : eval_fn_pinned(n, passes != EVAL_PLAIN);
   if (full) return eval_fn_full(n, keys);
   if (passes >= EVAL_MDTM) return eval_fn_mdtm(n, keys);
@@ -133,8 +136,8 @@ static const void* eval_fn(uint32_t n, bool full, bool keys, int passes, bool pi
   return eval_fn_topk(n, keys);
 }
 
-int eval_occupancy(uint32_t n, bool full, uint32_t bd, size_t shm, bool keys, int passes, bool pin) {
-  const void* k = eval_fn(n, full, keys, passes, pin);
+int eval_occupancy(uint32_t n, bool full, uint32_t bd, size_t shm, bool keys, int passes, bool pin, bool census) {
+  const void* k = eval_fn(n, full, keys, passes, pin, census);
   return k ? kernel_occupancy(k, bd, shm, 1) : 0;
 }
 
@@ -149,6 +152,18 @@ hipError_t launch_eval(const EvalArgs& a, uint32_t n, bool full, uint32_t grid, 
   static_cast<EvalArgs&>(pa) = a;
   pa.pz = *pin;
   return launch_kernel(k, pa, grid, bd, shm, st);
+}
+
+hipError_t launch_eval_census(const EvalArgs& a, uint32_t n, const CensusArgs& z, uint32_t grid, uint32_t bd,
+                              size_t shm, hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
+  const void* k = eval_fn(n, false, a.keys != 0, eval_passes(a.obj_kind, a.n_obj), false, true);
+  if (!k || a.cfgs || !z.thr || !z.below || z.T == 0 || z.T > (uint32_t)CENSUS_T || bd != 256)
+    return hipErrorInvalidValue;
+  CensusEvalArgs ca{};
+  static_cast<EvalArgs&>(ca) = a;
+  ca.out_top = nullptr;
+  ca.cz = z;
+  return launch_kernel(k, ca, grid, bd, shm, st, e0, e1);
 }
 
 hipError_t launch_single(const SingleArgs& a, int mode, hipStream_t st) {

@@ -228,6 +228,16 @@ struct BatchArgs {
 // host and the device pass number the enum differently, the mangled names
 // differ and the runtime does not find the kernel.
 constexpr int PIN_NONE = 0, PIN_ONE = 1, PIN_BATCH = 2;
+// A census launch (DESIGN.md §4 "Census sweeps", bote_census.hpp): per
+// objective T thresholds, ascending in (key, rank), and the counts they add to.
+// The census variants of the fast and the generic kernel take it at the end of
+// their arguments.
+constexpr int CENSUS_T = 16;  // thresholds per objective of a launch, at most
+struct CensusArgs {
+  const Rec* thr;             // [n_obj][T]
+  uint32_t T;                 // 1 .. CENSUS_T
+  unsigned long long* below;  // [n_obj][T]: += the configs before each threshold
+};
 #ifdef BOTE_DEBUG
 // bit `code` of *dbg_flag when `cond` fails (codes: DESIGN.md §5, debug build)
 #define GASSERT(a, cond, code)                                                    \
@@ -265,15 +275,20 @@ constexpr int PIN_NONE = 0, PIN_ONE = 1, PIN_BATCH = 2;
 // against each slot's mean) and carries no maxima or lists: a sweep with an
 // MDTM objective beside a MAX or percentile one runs the generic kernel
 enum { FAST_PLAIN = 0, FAST_MAX = 1, FAST_LIST = 2, FAST_MDTM = 3 };
-size_t fast_smem_bytes(const FastArgs& a, uint32_t n, int tail);
+// (census: the census variant, FAST_PLAIN and unpinned: thresholds and bins in place of the lists)
+size_t fast_smem_bytes(const FastArgs& a, uint32_t n, int tail, bool census = false);
 // (pin: PIN_*; the pinned and the batch variant are FAST_PLAIN only: SCORE, MEAN and COV objectives)
-int fast_occupancy(uint32_t n, int tail, int pin, size_t shm);
+int fast_occupancy(uint32_t n, int tail, int pin, size_t shm, bool census = false);
 // (e0, e1: events carried by the dispatch itself, bote_launch.hpp, for a timed launch)
 hipError_t launch_fast(const FastArgs& a, uint32_t n, int tail, const PinArgs* pin, uint32_t grid, size_t shm,
                        hipStream_t st, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
 // the batch variant (FAST_PLAIN) over the units of `b`; a.rb, a.re and a.runlen are not read
 hipError_t launch_fast_batch(const FastArgs& a, uint32_t n, const BatchArgs& b, uint32_t grid, size_t shm,
                              hipStream_t st, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
+// the census variant (FAST_PLAIN, unpinned) over [a.rb, a.re): adds to z.below, a.out_counters[0]
+// and the deferred queue; a.out_top and a.K are not read
+hipError_t launch_fast_census(const FastArgs& a, uint32_t n, const CensusArgs& z, uint32_t grid, size_t shm,
+                              hipStream_t st, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
 size_t group_smem_bytes(const FastArgs& a, uint32_t n);
 bool group_uses_lines(uint32_t n);  // n <= 7: client lines (FastArgs::gslots) and register lookups
 // the extended key set's group kernels target BOTE_GROUP_WAVES_XK waves per
@@ -312,9 +327,27 @@ inline int eval_passes(const uint32_t* obj_kind, int n_obj) {
 // sweep's overflow fallback, and MAX / percentile / MDTM objectives.  It has
 // EVAL_PLAIN and EVAL_MDTM; a percentile sweep takes EVAL_MDTM)
 int eval_occupancy(uint32_t n, bool full, uint32_t bd, size_t shm, bool keys = false, int passes = EVAL_PLAIN,
-                   bool pin = false);
+                   bool pin = false, bool census = false);
 hipError_t launch_eval(const EvalArgs& a, uint32_t n, bool full, uint32_t grid, uint32_t bd, size_t shm,
                        hipStream_t st, const PinArgs* pin = nullptr);
+// The census variant (base keys; EVAL_PLAIN, or EVAL_MDTM for a MAX, percentile
+// or MDTM objective) over the ranks [a.rb, a.re) or the rank list a.rank_list:
+// adds to z.below and a.out_counters[0]; a.out_top and a.K are not read, shm is
+// eval_smem_bytes with top-K structures.  On a rank list longer than a.re -
+// a.rb (the queue overflowed: the fallback counts the range) it counts nothing.
+hipError_t launch_eval_census(const EvalArgs& a, uint32_t n, const CensusArgs& z, uint32_t grid, uint32_t bd,
+                              size_t shm, hipStream_t st, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
+// A census launch's start: the n = n_obj x T thresholds (host memory, read before
+// the call returns) into the device table thr, and below[0 .. n), counters[0 .. 1]
+// and, where given, below_alt, counters_alt and *qcount zeroed
+hipError_t launch_census_begin(const Rec* host_thr, uint32_t n, Rec* thr, unsigned long long* below,
+                               unsigned long long* below_alt, unsigned long long* counters,
+                               unsigned long long* counters_alt, unsigned long long* qcount, hipStream_t st);
+// dst[0 .. n) = (sel && *sel > cap ? alt : src)[0 .. n), then dst[n] = the same choice
+// of csrc[0] / calt[0] (a census's counts and its valid count; alt, calt null without sel)
+hipError_t launch_census_pick(const unsigned long long* src, const unsigned long long* alt, uint32_t n,
+                              const unsigned long long* csrc, const unsigned long long* calt,
+                              const unsigned long long* sel, uint64_t cap, uint64_t* dst, hipStream_t st);
 
 // ---- top-K lists: merge, seed, counters (bote_merge.hip)
 // One level of the merge tree: every G_MERGE_LISTS lists of `src` (n_lists

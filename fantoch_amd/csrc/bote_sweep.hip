@@ -28,6 +28,7 @@
 // which is the sequence of the stages; the launcher.  What a variant FAST_*
 // adds to a config is in its tail carrier (bote_fast_tail.hpp), which has one
 // hook per stage.
+#include "bote_census.hpp"
 #include "bote_fast_tail.hpp"
 #include "bote_launch.hpp"
 #include "bote_pinned.hpp"
@@ -43,10 +44,11 @@ struct FastLds {
   size_t srv, cs1, cs2, vcol, binom;
   size_t top, cand, tmp, thr, cnt;  // TopkLds (cnt: 1 + MAXOBJ counters)
   size_t cmax, c4, ch;              // the tail variants' columns (TailCols)
+  size_t cthr, cbin;                // the census variant's thresholds and bins (CensusLds), in place of top, cand and tmp
   size_t total;
 };
 
-__host__ __device__ inline FastLds fast_layout(const FastArgs& a, int N, int NLW, int tail) {
+__host__ __device__ inline FastLds fast_layout(const FastArgs& a, int N, int NLW, int tail, bool census = false) {
   const auto a16 = [](size_t o) { return (o + 15) & ~(size_t)15; };
   FastLds l;
   size_t o = 0;
@@ -60,14 +62,17 @@ __host__ __device__ inline FastLds fast_layout(const FastArgs& a, int N, int NLW
   l.vcol = o; o += (size_t)a.ns * 8;
   l.binom = o; o += (size_t)(a.ns + 1) * (N + 1) * 8;
   o = a16(o);
-  l.top = o; o += (size_t)a.n_obj * KP * 16;
-  l.cand = o; o += (size_t)FAST_BD * 16;
-  l.tmp = o; o += (size_t)KP * 16;
+  l.top = o; o += census ? 0 : (size_t)a.n_obj * KP * 16;
+  l.cand = o; o += census ? 0 : (size_t)FAST_BD * 16;
+  l.tmp = o; o += census ? 0 : (size_t)KP * 16;
   l.thr = o; o += (size_t)MAXOBJ * 16;
   l.cnt = o; o += 48;
   l.cmax = o; o += tail == FAST_MAX ? (size_t)a.ns * 4 : 0;
   l.c4 = o; o += tail == FAST_LIST ? (size_t)a.ns * 8 : 0;  // (8-byte aligned: every region above is)
   l.ch = o; o += tail == FAST_MDTM ? (size_t)a.ns * 8 : 0;  // (the same)
+  if (census) o = a16(o);
+  l.cthr = o; o += census ? (size_t)a.n_obj * CENSUS_T * 16 : 0;
+  l.cbin = o; o += census ? (size_t)a.n_obj * CENSUS_T * 8 : 0;
   l.total = o;
   return l;
 }
@@ -79,7 +84,7 @@ constexpr int BATCH_LIM_WORD = 10;
 static_assert(1 + MAXOBJ <= BATCH_LIM_WORD && (BATCH_LIM_WORD + 2) * 4 <= 48 && BATCH_LIM_WORD % 2 == 0,
               "the limits follow the top-K counters inside the reserved 48 bytes, 8-byte aligned");
 
-size_t fast_smem_bytes(const FastArgs& a, uint32_t n, int tail) {
+size_t fast_smem_bytes(const FastArgs& a, uint32_t n, int tail, bool census) {
   int nl = 0;
   switch (n) {
 #define NL_CASE(NN) case NN: nl = QCfg<NN>::NL; break;
@@ -88,7 +93,7 @@ size_t fast_smem_bytes(const FastArgs& a, uint32_t n, int tail) {
 #undef NL_CASE
     default: return 0;
   }
-  return fast_layout(a, (int)n, nl <= 2 ? 1 : 2, tail).total;
+  return fast_layout(a, (int)n, nl <= 2 ? 1 : 2, tail, census).total;
 }
 
 struct FastSmem {
@@ -101,6 +106,7 @@ struct FastSmem {
   uint64_t* binom;
   TailCols tc;  // the tail variants' columns
   TopkLds tk;
+  CensusLds cl;  // the census variant's sink (tk.top, tk.cand and tmp are empty then; tk.thr holds the screen's keys)
 };
 
 __device__ __forceinline__ FastSmem fast_smem(const FastLds& l, unsigned char* smem) {
@@ -122,6 +128,8 @@ __device__ __forceinline__ FastSmem fast_smem(const FastLds& l, unsigned char* s
   s.tk.tmp = (Rec*)(smem + l.tmp);
   s.tk.thr = (Rec*)(smem + l.thr);
   s.tk.cnt = (int*)(smem + l.cnt);
+  s.cl.thr = (Rec*)(smem + l.cthr);
+  s.cl.bin = (unsigned long long*)(smem + l.cbin);
   return s;
 }
 
@@ -297,8 +305,9 @@ __device__ __forceinline__ void client_quads(const unsigned char* B, uint32_t cq
 }
 
 // ------------------------------------------------------------ the stages --
-// quad matrices, server list, binomials into LDS
-template <int N>
+// quad matrices, server list, binomials into LDS, and the empty block top-K
+// (CENSUS: no lists; the kernel fills the census sink itself)
+template <int N, bool CENSUS = false>
 __device__ __forceinline__ void stage_lds(const FastArgs& a, const FastSmem& s, uint32_t tid) {
   const uint32_t cw = a.R * a.cq_stride * 2;  // 32-bit words
   const uint32_t* src = (const uint32_t*)a.cqt;
@@ -312,7 +321,7 @@ __device__ __forceinline__ void stage_lds(const FastArgs& a, const FastSmem& s, 
   }
   for (uint32_t i = tid; i < a.ns; i += FAST_BD) s.srv[i] = a.srv[i];
   for (uint32_t i = tid; i < (a.ns + 1) * (N + 1); i += FAST_BD) s.binom[i] = a.binom[i];
-  topk_init(s.tk, a.n_obj);
+  if constexpr (!CENSUS) topk_init(s.tk, a.n_obj);
   __syncthreads();
 }
 
@@ -527,18 +536,27 @@ __device__ __forceinline__ void colocated(const unsigned char* B, const Leader& 
 // the planet once, then walks the batch's units blockIdx.x, += gridDim.x
 // (BatchArgs): per unit its own rank range and pinned set, a fresh block top-K
 // and fresh valid and digest sums, the unit's list slot and the set's counters.
-template <int N, int TAIL, int PIN = PIN_NONE>
-__global__ void __launch_bounds__(FAST_BD, 4) sweep_fast_kernel(typename Members<N, PIN>::Args a) {
+// CENSUS (FAST_PLAIN, unpinned; bote_census.hpp): the stages are the same up to
+// and including finish_config, which screens SCORE and COV keys with the
+// launch's largest thresholds; the sink is census_step in place of topk_step
+// and a flush of counts in place of the list dump.  A deferred config offers
+// no key (ok[] stays false), so it is counted for no objective here and for
+// every one by the generic kernel's census variant over the queue.
+template <int N, int TAIL, int PIN = PIN_NONE, bool CENSUS = false>
+__global__ void __launch_bounds__(FAST_BD, 4)
+    sweep_fast_kernel(std::conditional_t<CENSUS, CensusFastArgs, typename Members<N, PIN>::Args> a) {
   using TL = Tail<N, TAIL>;
   static_assert(PIN == PIN_NONE || TL::plain, "the pinned variants compute SCORE, MEAN and COV objectives");
+  static_assert(!CENSUS || (PIN == PIN_NONE && TL::plain), "the census variant is unpinned and computes SCORE, MEAN and COV objectives");
   constexpr bool BATCH = PIN == PIN_BATCH;
   constexpr int NL = TL::NL;
   extern __shared__ __align__(16) unsigned char smem[];
-  const FastSmem s = fast_smem(fast_layout(a, N, NL <= 2 ? 1 : 2, TAIL), smem);
+  const FastSmem s = fast_smem(fast_layout(a, N, NL <= 2 ? 1 : 2, TAIL, CENSUS), smem);
   const uint32_t tid = threadIdx.x;
   const unsigned char* B = smem;
 
-  stage_lds<N>(a, s, tid);
+  stage_lds<N, CENSUS>(a, s, tid);
+  if constexpr (CENSUS) census_init(s.cl, s.tk.thr, a.cz, a.n_obj, a.obj_kind);  // (published by the next stage's barrier)
   position_sums<TL>(a, s, tid);
 
   const uint32_t cstride = a.cq_stride * 8;  // bytes per CQT column
@@ -647,7 +665,8 @@ __global__ void __launch_bounds__(FAST_BD, 4) sweep_fast_kernel(typename Members
             }
           }
         }
-        if (!ABLATE(a, 4)) topk_step(s.tk, a.n_obj, a.K, key, ok, frank);
+        if constexpr (CENSUS) census_step(s.cl, a.n_obj, a.cz.T, key, ok, frank);
+        else if (!ABLATE(a, 4)) topk_step(s.tk, a.n_obj, a.K, key, ok, frank);
         mb.next(a.ns, pz, jobok && rank < re);
         ++rank;
       }
@@ -663,7 +682,9 @@ __global__ void __launch_bounds__(FAST_BD, 4) sweep_fast_kernel(typename Members
     if (valid_cnt) atomicAdd(&counters[0], (unsigned long long)valid_cnt);
     if (digest) atomicAdd(&counters[1], (unsigned long long)digest);
     __syncthreads();
-    for (uint32_t i = tid; i < (uint32_t)a.n_obj * KP; i += FAST_BD) dst[i] = s.tk.top[i];
+    if constexpr (CENSUS) census_flush(s.cl, a.cz, a.n_obj);
+    else
+      for (uint32_t i = tid; i < (uint32_t)a.n_obj * KP; i += FAST_BD) dst[i] = s.tk.top[i];
     if constexpr (BATCH) more = (unit += gridDim.x) < a.bz.n_sets * a.bz.slices;
   } while (more);
 }
@@ -672,10 +693,14 @@ __global__ void __launch_bounds__(FAST_BD, 4) sweep_fast_kernel(typename Members
 // the kernel for config size n (null: unsupported; the pinned and the batch
 // variant, pin = PIN_*, are FAST_PLAIN only), for the occupancy query and the
 // launch alike
-static const void* fast_fn(uint32_t n, int tail, int pin) {
+static const void* fast_fn(uint32_t n, int tail, int pin, bool census = false) {
   switch (n) {
 #define FN_CASE(NN)                                                                  \
   case NN:                                                                           \
+    if (census)                                                                      \
+      return tail == FAST_PLAIN && pin == PIN_NONE                                   \
+                 ? (const void*)sweep_fast_kernel<NN, FAST_PLAIN, PIN_NONE, true>    \
+                 : nullptr;                                                          \
     if (pin == PIN_BATCH) return tail == FAST_PLAIN ? (const void*)sweep_fast_kernel<NN, FAST_PLAIN, PIN_BATCH> : nullptr; \
     if (pin == PIN_ONE) return tail == FAST_PLAIN ? (const void*)sweep_fast_kernel<NN, FAST_PLAIN, PIN_ONE> : nullptr; \
     return tail == FAST_MDTM   ? (const void*)sweep_fast_kernel<NN, FAST_MDTM>       \
@@ -689,8 +714,8 @@ static const void* fast_fn(uint32_t n, int tail, int pin) {
   }
 }
 
-int fast_occupancy(uint32_t n, int tail, int pin, size_t shm) {
-  const void* k = fast_fn(n, tail, pin);
+int fast_occupancy(uint32_t n, int tail, int pin, size_t shm, bool census) {
+  const void* k = fast_fn(n, tail, pin, census);
   return k ? kernel_occupancy(k, FAST_BD, shm, 1) : 0;
 }
 
@@ -703,6 +728,16 @@ hipError_t launch_fast(const FastArgs& a, uint32_t n, int tail, const PinArgs* p
   static_cast<FastArgs&>(pa) = a;
   pa.pz = *pin;
   return launch_kernel(k, pa, grid, FAST_BD, shm, st, e0, e1);
+}
+
+hipError_t launch_fast_census(const FastArgs& a, uint32_t n, const CensusArgs& z, uint32_t grid, size_t shm,
+                              hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
+  const void* k = fast_fn(n, FAST_PLAIN, PIN_NONE, true);
+  if (!k || !z.thr || !z.below || z.T == 0 || z.T > (uint32_t)CENSUS_T) return hipErrorInvalidValue;
+  CensusFastArgs ca{};
+  static_cast<FastArgs&>(ca) = a;
+  ca.cz = z;
+  return launch_kernel(k, ca, grid, FAST_BD, shm, st, e0, e1);
 }
 
 hipError_t launch_fast_batch(const FastArgs& a, uint32_t n, const BatchArgs& b, uint32_t grid, size_t shm,

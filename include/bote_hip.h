@@ -464,6 +464,65 @@ int bote_batch_plan(const bote_batch* b, uint32_t* out_slices, uint64_t* out_uni
 /* May be called after the planet is destroyed, like bote_sweep_destroy. */
 int bote_batch_destroy(bote_batch* b);
 
+/* ------------------------------------------------------ census sweeps --- */
+/* Where a configuration stands among all C(ns, n): counts of the configs
+ * ranked before given records, not lists.  (The reference stores every config,
+ * search.rs:234-260, and a sort gives a config's place; the streaming sweep
+ * keeps 128 records per objective, so a config outside them has no position.)
+ * A census takes bote_sweep_create_ex's arguments without K and digest, on the
+ * base key set.  A launch takes a rank range [rank_begin, rank_end) and, per
+ * objective, T threshold records, 1 <= T <= BOTE_CENSUS_MAX_THRESHOLDS, the
+ * same T for every objective: thr[o * T + t].  For objective o and threshold t
+ *   below[o * T + t] = |{ r in [rank_begin, rank_end) : the sweep would offer
+ *                         config r to objective o's list, and
+ *                         (key_o(r), r) < (thr[o * T + t].key, .rank) }|
+ * with key_o the key bote_topk_record defines for the objective's kind and the
+ * order the unsigned lexicographic (key, rank) order of the lists.  "Would
+ * offer" is the sweep's rule: a SCORE objective ranks only the configs with a
+ * valid compute_score, every other kind ranks every config (a COV key of ~0
+ * included).  out_valid is bote_sweep_result's (only with a SCORE objective),
+ * so objective o's population is the valid count for SCORE and rank_end -
+ * rank_begin otherwise.  Record i (0-based) of a full sweep's list for
+ * objective o has below == i.  Counts of disjoint rank ranges add.
+ * The thresholds of one objective must ascend in (key, rank); equal neighbours
+ * are allowed, anything else is BOTE_E_ARG.  Any u64 is a legal threshold key:
+ * thresholds need not be records of real configs ((0, 0), (~0, ~0), a COV key
+ * that is no finite non-negative double).  A config whose key equals a
+ * threshold's is before it only when its rank is lower: none is before (k, 0).
+ * Routing as for pinned sweeps: AUTO or forced fast on an eligible planet with
+ * only SCORE, MEAN and COV objectives runs the fast kernel's census variant
+ * (its deferred configs are counted by the generic kernel's rank-list fix-up,
+ * and a launch that overflows the deferred queue is counted once, whole, on the
+ * generic kernel: both decided on the device); a MAX, percentile or MDTM
+ * objective, an ineligible planet and a forced generic kernel run the generic
+ * kernel's census variant; a forced fast kernel with such an objective and a
+ * forced group kernel are BOTE_E_ARG. */
+#define BOTE_CENSUS_MAX_THRESHOLDS 16
+typedef struct bote_census bote_census;
+int bote_census_create(const bote_planet* p, const uint32_t* servers, uint32_t ns,
+                       const uint32_t* clients, uint32_t nc, uint32_t n,
+                       const bote_objective* objs, uint32_t n_obj,
+                       const bote_ranking_params* rp, int kernel, bote_census** out);
+/* Asynchronous on `hip_stream`, like bote_sweep_launch; `thr` (n_obj x T, host)
+ * is copied before the call returns.  Each launch restarts the counts, and T
+ * may differ between the launches of one handle. */
+int bote_census_launch(bote_census* c, const bote_topk_record* thr, uint32_t T,
+                       uint64_t rank_begin, uint64_t rank_end, void* hip_stream);
+/* Synchronises `hip_stream`.  out_below: n_obj x T of the last launch;
+ * out_valid as bote_sweep_result's (either may be null). */
+int bote_census_result(bote_census* c, void* hip_stream, uint64_t* out_below, uint64_t* out_valid);
+/* Configs the fast kernel deferred in the last launch (more than 2^20: the
+ * whole range was counted on the generic kernel).  Synchronises `hip_stream`.
+ * 0 on the generic path. */
+int bote_census_deferred(bote_census* c, void* hip_stream, uint64_t* out);
+/* 0 generic, 1 fast (bote_sweep_is_fast's values). */
+int bote_census_path(const bote_census* c, int* out);
+/* Kernel-only time of the last launch's census kernel in ms (the fix-up and
+ * the fallback excluded, as bote_sweep_last_kernel_ms). */
+int bote_census_last_kernel_ms(bote_census* c, float* out_ms);
+/* May be called after the planet is destroyed, like bote_sweep_destroy. */
+int bote_census_destroy(bote_census* c);
+
 /* ------------------------------------------------ multi-device search --- */
 /* The exhaustive search over colex ranks [rank_begin, rank_end) sharded over
  * n_devices planets (planets[i] lives on the device that sweeps shard i; a

@@ -43,6 +43,9 @@ pub const fn bote_obj_pctl(bp: u32) -> u32 {
 /// H = the sum over the slot's values above its mean of (count * x - sum); mdtm = 2 H / count^2
 pub const BOTE_OBJ_MDTM: u32 = 18;
 
+/// thresholds per objective of one bote_census_launch, at most
+pub const BOTE_CENSUS_MAX_THRESHOLDS: u32 = 16;
+
 #[repr(C)]
 pub struct bote_planet {
     _p: [u8; 0],
@@ -53,6 +56,10 @@ pub struct bote_sweep {
 }
 #[repr(C)]
 pub struct bote_batch {
+    _p: [u8; 0],
+}
+#[repr(C)]
+pub struct bote_census {
     _p: [u8; 0],
 }
 #[repr(C)]
@@ -183,6 +190,17 @@ extern "C" {
                                      prev_s1: *const u64, out: *mut *mut bote_batch) -> c_int;
     pub fn bote_batch_limits(b: *const bote_batch, out: *mut u32) -> c_int;
     pub fn bote_mean_decrease_limit(prev_s1: u64, count: u32, min_mean_decrease: f64, out_limit: *mut u32) -> c_int;
+    pub fn bote_census_create(p: *const bote_planet, servers: *const u32, ns: u32, clients: *const u32, nc: u32,
+                              n: u32, objs: *const bote_objective, n_obj: u32, rp: *const bote_ranking_params,
+                              kernel: c_int, out: *mut *mut bote_census) -> c_int;
+    pub fn bote_census_launch(c: *mut bote_census, thr: *const bote_topk_record, t: u32, rank_begin: u64,
+                              rank_end: u64, stream: *mut c_void) -> c_int;
+    pub fn bote_census_result(c: *mut bote_census, stream: *mut c_void, out_below: *mut u64, out_valid: *mut u64)
+        -> c_int;
+    pub fn bote_census_deferred(c: *mut bote_census, stream: *mut c_void, out: *mut u64) -> c_int;
+    pub fn bote_census_path(c: *const bote_census, out: *mut c_int) -> c_int;
+    pub fn bote_census_last_kernel_ms(c: *mut bote_census, out_ms: *mut f32) -> c_int;
+    pub fn bote_census_destroy(c: *mut bote_census) -> c_int;
 }
 
 /// Turns a status code into the panic the reference raises at the same place
