@@ -71,6 +71,7 @@ EXPORTS = [
     "bote_batch_create_bounded", "bote_batch_limits", "bote_mean_decrease_limit",
     "bote_census_create", "bote_census_launch", "bote_census_result", "bote_census_deferred", "bote_census_path",
     "bote_census_last_kernel_ms", "bote_census_destroy",
+    "bote_sweep_create_constrained", "bote_sweep_admitted",
 ]
 KERNELS = {None: 0, "auto": 0, "generic": 1, "fast": 2, "group": 3}
 
@@ -83,6 +84,11 @@ class BoteError(RuntimeError):
 
 class Objective(C.Structure):
     _fields_ = [("kind", C.c_uint32), ("slot", C.c_uint32)]
+
+
+class Constraint(C.Structure):
+    """bote_constraint: a config is admitted iff the (kind, slot) key is <= max_key."""
+    _fields_ = [("kind", C.c_uint32), ("slot", C.c_uint32), ("max_key", C.c_uint64)]
 
 
 class RankingParamsC(C.Structure):
@@ -218,6 +224,12 @@ def lib():
         L.bote_census_path.argtypes = [_vp, C.POINTER(C.c_int)]
         L.bote_census_last_kernel_ms.argtypes = [_vp, C.POINTER(C.c_float)]
         L.bote_census_destroy.argtypes = [_vp]
+    if hasattr(L, "bote_sweep_create_constrained"):  # (the same)
+        L.bote_sweep_create_constrained.argtypes = [_vp, _u32p, C.c_uint32, _u32p, C.c_uint32, C.c_uint32,
+                                                    C.POINTER(Objective), C.c_uint32, C.POINTER(Constraint),
+                                                    C.c_uint32, C.c_uint32, C.POINTER(RankingParamsC), C.c_int,
+                                                    C.c_int, C.POINTER(_vp)]
+        L.bote_sweep_admitted.argtypes = [_vp, _vp, C.POINTER(C.c_uint64)]
     if hasattr(L, "bote_percentile_index"):  # (absent from an older BOTE_LIB_PATH build loaded for A/B timing)
         L.bote_percentile_index.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_int)]
     _LIB = L

@@ -14,14 +14,16 @@ import enum
 import itertools
 import math
 import os
+import re
 from dataclasses import dataclass
+from decimal import Decimal
 from fractions import Fraction
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
 from . import _lib, bincode
-from ._lib import check, lib, ptr, u32
+from ._lib import BoteError, check, lib, ptr, u32
 from .metrics import F64, Histogram, Stats
 from .planet import Planet, Region
 from .protocol import ClientPlacement, Protocol, ProtocolStats
@@ -730,6 +732,87 @@ def pctl_kind(p: float) -> int:
     return _lib.OBJ_PCTL(bp)
 
 
+# ---- bounds of a constrained sweep (Sweep(constraints=...), bote_sweep_create_constrained)
+# A constraint (kind, slot, max_key) admits the configs whose (kind, slot) key
+# is <= max_key.  The helpers turn "statistic <= v" into the largest such key,
+# exactly: v is an int, a Fraction, a Decimal or a decimal string (a float
+# stands for the binary value it holds), `count` the values of the slot (the
+# clients, or n for a colocated slot), and all arithmetic is rational.  A COV
+# bound is a key: a record's, or one of Census.quantiles.
+def _exact(v) -> Fraction:
+    f = Fraction(v) if not isinstance(v, str) else Fraction(Decimal(v.strip()))
+    if f < 0:
+        raise ValueError(f"a bound of {v} admits nothing: latencies are not negative")
+    return f
+
+
+def mean_bound(v, count: int) -> int:
+    """mean <= v as an OBJ_MEAN bound: the sums S1 <= floor(v * count)."""
+    return math.floor(_exact(v) * int(count))
+
+
+def max_bound(m) -> int:
+    """max <= m as an OBJ_MAX bound: every sum under the largest admitted maximum."""
+    return math.floor(_exact(m)) << 32 | 0xFFFFFFFF
+
+
+def pctl_bound(v) -> int:
+    """percentile <= v as an OBJ_PCTL bound (the key holds twice the percentile, an integer)."""
+    return math.floor(2 * _exact(v)) << 32 | 0xFFFFFFFF
+
+
+def mdtm_bound(v, count: int) -> int:
+    """mdtm <= v as an OBJ_MDTM bound: mdtm = 2 H / count^2, so H <= floor(v * count^2 / 2)."""
+    return math.floor(_exact(v) * int(count) ** 2 / 2) << _lib.MDTM_SUM_BITS | ((1 << _lib.MDTM_SUM_BITS) - 1)
+
+
+_WHERE = re.compile(r"^\s*([A-Za-z0-9.]+)\s*:\s*([A-Za-z0-9]+)\s*<=\s*(.+?)\s*$")
+_NUMBER = re.compile(r"^[0-9]+(\.[0-9]+)?$")
+
+
+def parse_where(text: str, nc: int, n: int) -> List[Tuple[int, int, int]]:
+    """Constraints from 'mean:ff1<=140,p99:af1<=300,cov:ff1C<=key:0x3f9...': comma-separated
+    KIND:SLOT<=VALUE with KIND mean, cov, max, mdtm or pNN[.NN] (a percentile), SLOT a name of
+    _lib.SLOT_NAMES, and VALUE a decimal number (parsed exactly, never through a float) or
+    key:INTEGER, the bound as a raw key (the only form a cov bound takes).  nc, n: the clients
+    and the config size, which give each slot's count."""
+    out = []
+    for item in text.split(","):
+        m = _WHERE.match(item)
+        if not m:
+            raise ValueError(f"constraint {item!r} is not KIND:SLOT<=VALUE")
+        kind_s, slot_s, val = m.group(1).lower(), m.group(2), m.group(3)
+        if slot_s not in _lib.SLOT_NAMES:
+            raise ValueError(f"unknown slot {slot_s!r} (one of {', '.join(_lib.SLOT_NAMES)})")
+        slot = _lib.SLOT_NAMES.index(slot_s)
+        count = n if slot >= 5 else nc
+        if kind_s in ("mean", "cov", "max", "mdtm"):
+            kind = {"mean": _lib.OBJ_MEAN, "cov": _lib.OBJ_COV, "max": _lib.OBJ_MAX, "mdtm": _lib.OBJ_MDTM}[kind_s]
+        elif kind_s.startswith("p") and _NUMBER.match(kind_s[1:]):
+            bp = Fraction(Decimal(kind_s[1:])) * 100
+            if bp.denominator != 1 or not 1 <= bp <= 9999:
+                raise ValueError(f"percentile {kind_s!r} is not a multiple of 0.01 in 0.01 .. 99.99")
+            kind = _lib.OBJ_PCTL(int(bp))
+        else:
+            raise ValueError(f"unknown constraint kind {kind_s!r} (mean, cov, max, mdtm or pNN)")
+        if val.lower().startswith("key:"):
+            try:
+                key = int(val[4:].strip(), 0)
+            except ValueError:
+                raise ValueError(f"constraint {item!r}: key: takes an integer") from None
+            if not 0 <= key < 1 << 64:
+                raise ValueError(f"constraint {item!r}: the key is not a 64-bit unsigned integer")
+        elif kind == _lib.OBJ_COV:
+            raise ValueError("a cov bound is a key (cov:SLOT<=key:0x...): a record's, or a census quantile")
+        elif not _NUMBER.match(val):
+            raise ValueError(f"constraint {item!r}: {val!r} is not a decimal number")
+        else:
+            key = (mean_bound(val, count) if kind == _lib.OBJ_MEAN else max_bound(val) if kind == _lib.OBJ_MAX
+                   else mdtm_bound(val, count) if kind == _lib.OBJ_MDTM else pctl_bound(val))
+        out.append((kind, slot, key))
+    return out
+
+
 @dataclass
 class SweepResult:
     tops: List[List[Tuple[int, int]]]  # per objective: (key, rank) ascending
@@ -743,14 +826,22 @@ class Sweep:
     def __init__(self, dp: DevicePlanet, servers: Sequence[int], clients: Sequence[int], n: int,
                  objectives=DEFAULT_OBJECTIVES, K: int = 100, ranking: Optional[RankingParams] = DEFAULT_RANKING,
                  digest: bool = False, kernel: Optional[str] = None, keys: int = _lib.KEYS_BASE,
-                 pinned: Optional[Sequence[int]] = None):
+                 pinned: Optional[Sequence[int]] = None,
+                 constraints: Optional[Sequence[Tuple[int, int, int]]] = None):
         """kernel: None/'auto' (the library's choice), or force 'generic', 'fast'
         or 'group' (every path is exact; bote_sweep_create_keys).  keys: the
         key set (_lib.KEYS_BASE, or KEYS_TEMPO_ALL_LEADERS for BASELINE config 5).
         pinned: positions into `servers` that every swept config contains
         (bote_sweep_create_pinned, base key set): `total`, `launch` and `split`
-        then count pinned ranks, and records still carry full colex ranks."""
+        then count pinned ranks, and records still carry full colex ranks.
+        constraints: (kind, slot, max_key) triples (bote_sweep_create_constrained,
+        base key set, unpinned; an empty list too takes that entry): only the configs
+        whose (kind, slot) key is <= max_key for every triple are offered to the
+        lists; the valid count and the digest stay the unconstrained sweep's, and
+        admitted() counts the configs that met the bounds (mean_bound, max_bound,
+        pctl_bound, mdtm_bound and parse_where make bounds)."""
         self.dp, self.n, self.K, self.keys = dp, n, K, keys
+        self.constraints = None if constraints is None else [(int(k), int(s), int(b)) for k, s, b in constraints]
         self.pinned = None if pinned is None else u32(pinned)
         self.servers, self.clients = u32(servers), u32(clients)
         self.objectives = list(objectives)
@@ -767,6 +858,17 @@ class Sweep:
                                                  _lib.KERNELS[kernel], C.byref(h)))
             self.h = h
             self.total = _lib.pinned_total(len(self.servers), n, len(self.pinned))
+            return
+        if self.constraints is not None:
+            if keys != _lib.KEYS_BASE:
+                raise BoteError(-1, "constrained sweeps compute the base key set")
+            cons = (_lib.Constraint * max(len(self.constraints), 1))(*[_lib.Constraint(*c) for c in self.constraints])
+            check(lib().bote_sweep_create_constrained(dp.h, self.servers, len(self.servers), self.clients,
+                                                      len(self.clients), n, objs, len(self.objectives), cons,
+                                                      len(self.constraints), K, rp, 1 if digest else 0,
+                                                      _lib.KERNELS[kernel], C.byref(h)))
+            self.h = h
+            self.total = _lib.binomial(len(self.servers), n)
             return
         check(lib().bote_sweep_create_keys(dp.h, self.servers, len(self.servers), self.clients, len(self.clients), n,
                                            objs, len(self.objectives), K, rp, 1 if digest else 0,
@@ -809,6 +911,9 @@ class Sweep:
                                 np.asarray(self.dp.planet.lat, np.uint64).reshape(-1)])
         if self.pinned is not None:  # (a checkpoint of another pinned set, or of the unpinned sweep, is refused)
             ident = np.concatenate([ident, np.array([len(self.pinned)], np.uint64), self.pinned.astype(np.uint64)])
+        if self.constraints:  # (a checkpoint under other bounds, or of the unconstrained sweep, is refused)
+            ident = np.concatenate([ident, np.array([1 << 32 | len(self.constraints)], np.uint64),
+                                    np.asarray(self.constraints, np.uint64).reshape(-1)])
         dev = torch.device("cuda", self.dp.device)
         st = torch.cuda.current_stream(dev).cuda_stream
         nb = self.result_bytes()
@@ -897,6 +1002,13 @@ class Sweep:
         """Configs the last launch deferred to the exact generic kernel."""
         v = C.c_uint64()
         check(lib().bote_sweep_deferred(self.h, C.c_void_p(stream) if stream else None, C.byref(v)))
+        return v.value
+
+    def admitted(self, stream: Optional[int] = None) -> int:
+        """Configs of the last launch's range that meet every constraint (the range's size
+        on a sweep without constraints); counts of disjoint ranges add."""
+        v = C.c_uint64()
+        check(lib().bote_sweep_admitted(self.h, C.c_void_p(stream) if stream else None, C.byref(v)))
         return v.value
 
     def is_fast(self) -> bool:

@@ -21,6 +21,7 @@ main.rs:31-60).  Subcommands expose them, and the sweep the hot path serves:
                         [--objectives default|config5|mean:af1,cov:af1,max:af1,p95:af1,p99.9:e,mdtm:af1,score,...]
                         [--keys base|tempo-all-leaders] [--gpus G] [--rank-begin B --rank-end E]
                         [--pinned a,b | --pinned 3,9 | --pinned-sets "a,b;c,d"]
+                        [--where "mean:ff1<=140,p99:af1<=300,cov:ff1C<=key:0x3f..."]
   python -m fantoch_amd evolve (--synthetic R [--seed S] | --lat-dir D [--input R13C13|R17C17|R20C20])
                         [--min-n 3] [--max-n 13] [--beam B] [-K 100] [--ranking 110,35,0,15] [--ft F1F2]
                         [--chains 1]
@@ -202,7 +203,8 @@ def sweep(args, out=sys.stdout):
     import numpy as np
 
     from . import _lib
-    from .bote import DEFAULT_RANKING, DevicePlanet, MultiDeviceSearch, PinnedBatch, Sweep, max_key, mdtm_key, pctl_key
+    from .bote import (DEFAULT_RANKING, DevicePlanet, MultiDeviceSearch, PinnedBatch, Sweep, max_key, mdtm_key,
+                       parse_where, pctl_key)
 
     planet = _planet(args)
     srv = np.arange(planet.R, dtype=np.uint32)
@@ -217,6 +219,11 @@ def sweep(args, out=sys.stdout):
             raise ValueError("--pinned-sets and --pinned exclude each other")
         if args.gpus > 1 or keys != _lib.KEYS_BASE or args.rank_begin is not None or args.rank_end is not None:
             raise ValueError("--pinned-sets sweeps every set's whole rank space on one device with the base key set")
+    where = getattr(args, "where", None)
+    cons = parse_where(where, planet.R, args.n) if where else None
+    if cons is not None and (args.gpus > 1 or keys != _lib.KEYS_BASE or pinned is not None or sets is not None):
+        raise ValueError("--where sweeps run unpinned on one device with the base key set")
+    admitted = None
     # (--rank-begin / --rank-end of a pinned sweep are pinned ranks)
     total = _lib.binomial(planet.R, args.n) if pinned is None else _lib.pinned_total(planet.R, args.n, len(pinned))
     rb = args.rank_begin or 0
@@ -235,9 +242,10 @@ def sweep(args, out=sys.stdout):
         res = h.result()
     else:
         sw = Sweep(DevicePlanet(planet, args.device), srv, srv, args.n, objs, K=args.K, ranking=DEFAULT_RANKING,
-                   digest=True, keys=keys, pinned=pinned)
+                   digest=True, keys=keys, pinned=pinned, constraints=cons)
         sw.launch(rb, re)
         res = sw.result()
+        admitted = sw.admitted() if cons is not None else None
 
     def regions(rank):
         return [planet.names[i] for i in _lib.colex_unrank(int(rank), args.n, planet.R)]
@@ -264,6 +272,9 @@ def sweep(args, out=sys.stdout):
                               for o, (k, s) in enumerate(objs)]}
         if pinned is not None:
             doc["pinned"] = pinned
+        if admitted is not None:  # beside the valid count: "admitted N of TOTAL"
+            doc["where"], doc["admitted"] = where, admitted
+            doc["admitted_of"] = f"admitted {admitted} of {re - rb}"
         print(json.dumps(doc, indent=None if args.compact else 1), file=out)
         return doc
 
@@ -425,6 +436,10 @@ def build_parser() -> argparse.ArgumentParser:
                    help="region names or positions every swept config contains (rank flags are then pinned ranks)")
     p.add_argument("--pinned-sets", default=None,
                    help="';'-separated --pinned lists of one size: one launch sweeps every set, one block per set")
+    p.add_argument("--where", default=None,
+                   help="rank only the configs within key bounds: KIND:SLOT<=VALUE[,...], e.g. "
+                        "'mean:ff1<=140,p99:af1<=300,cov:ff1C<=key:0x3f9...' (mean, cov, max, mdtm, pNN; a cov "
+                        "bound is a raw key); prints the admitted count beside the valid count")
     p.add_argument("--compact", action="store_true")
     p = sub.add_parser("evolve", allow_abbrev=False, help="streaming evolving search: bounded pinned batches and a beam")
     planet_flags(p, synthetic=True)

@@ -221,6 +221,15 @@ struct bote_sweep {
   // pinned positions and its rank space C(ns - pin_n, n - pin_n)
   bote::PinArgs pz{};
   uint64_t ptotal = 0;
+  // a constrained sweep (bote_sweep_create_constrained; n_con == 0: none):
+  // args and fargs then hold n_obj + n_con key entries, the constraints last,
+  // and `con` is what the constrained kernel variants take beside them
+  // (bounds by key entry; its counter is set per launch).  admitted: [0] the
+  // fast kernel's and its fix-up's count, or the generic path's; [1] the
+  // overflow fallback's
+  uint32_t n_con = 0;
+  bote::ConArgs con{};
+  DBuf admitted;
   uint64_t last_rb = 0, last_re = 0;
   hipStream_t last_stream = nullptr;
   uint64_t result_bytes() const { return (uint64_t)n_obj * bote::KP * 16 + 16; }

@@ -60,11 +60,12 @@ static_assert(PCTL_MAX_NEED == (uint32_t)bote::PCTL_DEPTH && bote::PCTL_DEPTH <=
 
 // Step 2: the server, client and binomial lists on the device, the generic
 // kernel's arguments (s->args) and its launch geometry.
+// (objs: the n_obj key entries, a constrained sweep's constraints after its objectives)
 static int sweep_upload_lists(bote_sweep* s, const uint32_t* servers, const uint32_t* clients,
-                              const bote_objective* objs, const bote_ranking_params* rp, bool has_score, int digest,
-                              uint32_t keys) {
+                              const bote_objective* objs, uint32_t n_obj, const bote_ranking_params* rp,
+                              bool has_score, int digest, uint32_t keys) {
   const bote_planet* p = s->p;
-  const uint32_t n = s->n, ns = s->ns, nc = s->nc, n_obj = s->n_obj;
+  const uint32_t n = s->n, ns = s->ns, nc = s->nc;
   EvalArgs& a = s->args;
   a = EvalArgs{};
   auto t = binom_table(ns, n);
@@ -102,7 +103,7 @@ static int sweep_upload_lists(bote_sweep* s, const uint32_t* servers, const uint
   a.out_top = nullptr;
   if (s->shm > device_max_lds(p->device)) return fail(BOTE_E_RANGE, "planet/client set too large for LDS");
   const int passes = bote::eval_passes(a.obj_kind, (int)n_obj);
-  int nb = bote::eval_occupancy(n, false, s->bd, s->shm, keys != 0, passes, s->pz.pin_n != 0);
+  int nb = bote::eval_occupancy(n, false, s->bd, s->shm, keys != 0, passes, s->pz.pin_n != 0, false, s->n_con != 0);
   s->grid = (uint32_t)(device_cus(p->device) * nb);
   s->xgrid = 32;
   return BOTE_OK;
@@ -174,7 +175,8 @@ static int sweep_plan_group(bote_sweep* s, const FastLimits& lim, bool compiled_
   bote::FastArgs& f = s->fargs;
   // (a MAX, percentile or MDTM objective: the fast kernel's variant, s->tail; a
   // forced group kernel was refused with the arguments, check_sweep_args)
-  bool want_group = n >= 4 && ns <= 256 && group_utilisation(ns, n) >= 0.9 && !s->tail && !s->pz.pin_n;
+  // (nor a constrained sweep: the group kernel does not apply constraints)
+  bool want_group = n >= 4 && ns <= 256 && group_utilisation(ns, n) >= 0.9 && !s->tail && !s->pz.pin_n && !s->n_con;
   if (kernel != BOTE_KERNEL_AUTO) want_group = n >= 4 && ns <= 256 && kernel == BOTE_KERNEL_GROUP;
   if (kernel == BOTE_KERNEL_GROUP && !want_group) return fail(BOTE_E_ARG, "group kernel needs n >= 4");
   if (s->path == Path::Generic || !want_group) return BOTE_OK;
@@ -302,19 +304,16 @@ static int sweep_plan_fast(bote_sweep* s, const uint32_t* servers, const uint32_
   // an MDTM objective: the fast kernel's MDTM variant (base key set), which
   // carries no maxima or lists, so with a MAX or percentile objective beside
   // it the generic kernel
-  s->tail = bote::FAST_PLAIN;
-  uint32_t need = 0;
-  bool mdtm = false;
-  for (uint32_t o = 0; o < s->n_obj; ++o) {
-    if (a.obj_kind[o] == BOTE_OBJ_MAX) s->tail = std::max(s->tail, (int)bote::FAST_MAX);
-    if (a.obj_kind[o] >= bote::OBJ_PCTL) {
-      s->tail = bote::FAST_LIST;
-      need = std::max(need, a.obj_kind[o] & bote::PCTL_NEED_MASK);
-    }
-    mdtm = mdtm || a.obj_kind[o] == BOTE_OBJ_MDTM;
-  }
-  const bool mdtm_mixed = mdtm && s->tail != bote::FAST_PLAIN;
-  if (mdtm) s->tail = bote::FAST_MDTM;
+  // (fast_tail_plan, over the key entries: a constrained sweep's constraints
+  // count as its objectives do)
+  static_assert(TAIL_PLAIN == bote::FAST_PLAIN && TAIL_MAX == bote::FAST_MAX && TAIL_LIST == bote::FAST_LIST &&
+                    TAIL_MDTM == bote::FAST_MDTM && DEV_KIND_PCTL == bote::OBJ_PCTL &&
+                    DEV_PCTL_NEED_MASK == bote::PCTL_NEED_MASK,
+                "the host plan speaks of the kernels' variants and kinds");
+  const TailPlan tp = fast_tail_plan(a.obj_kind, (uint32_t)a.n_obj);
+  s->tail = tp.tail;
+  const uint32_t need = tp.need;
+  const bool mdtm_mixed = tp.mixed;
   // a pinned sweep: the fast kernel's pinned variant computes SCORE, MEAN and
   // COV objectives; every other sweep of pinned members runs the generic
   // kernel's pinned variant (launch_sweep_eval)
@@ -344,6 +343,12 @@ static int sweep_plan_fast(bote_sweep* s, const uint32_t* servers, const uint32_
                               "percentile objectives runs the generic kernel, which computes both");
     s->path = Path::Generic;
   }
+  // a constrained sweep on a variant whose constrained kernel is not built
+  if (s->n_con && s->path != Path::Generic && !bote::fast_has_constrained(n, s->tail)) {
+    if (kernel == BOTE_KERNEL_FAST)
+      return fail(BOTE_E_ARG, "the fast kernel's constrained variant is not built for these kinds (generic kernel)");
+    s->path = Path::Generic;
+  }
   if (s->path == Path::Generic) return BOTE_OK;
   int rc;
   if ((rc = fill_fast_args(s, servers, clients, lim))) return rc;
@@ -366,7 +371,8 @@ static int sweep_plan_fast(bote_sweep* s, const uint32_t* servers, const uint32_
   if (s->fshm > device_max_lds(p->device)) {
     s->path = Path::Generic;
   } else {
-    s->fgrid = (uint32_t)(device_cus(p->device) * bote::fast_occupancy(n, s->tail, s->pz.pin_n != 0, s->fshm));
+    s->fgrid = (uint32_t)(device_cus(p->device) *
+                          bote::fast_occupancy(n, s->tail, s->pz.pin_n != 0, s->fshm, false, s->n_con != 0));
   }
   if ((rc = sweep_plan_group(s, lim, compiled_objs, kernel))) return rc;
   // the fast (non-group) kernel does not compute the extended key set
@@ -389,7 +395,9 @@ static int sweep_alloc_workspace(bote_sweep* s) {
   if (fixup && (s->top_alt.alloc((size_t)s->grid * std::max<uint32_t>(n_obj, 1) * bote::KP * 16) != hipSuccess ||
                   s->counters_alt.alloc(16) != hipSuccess))
     return fail(BOTE_E_NOMEM, "hipMalloc overflow fallback workspace");
-  s->args.out_top = n_obj ? s->top.as<Rec>() : nullptr;
+  if (s->n_con && s->admitted.alloc(16) != hipSuccess) return fail(BOTE_E_NOMEM, "hipMalloc admitted counters");
+  // (a constrained sweep without objectives still builds its keys: the admitted count)
+  s->args.out_top = n_obj || s->n_con ? s->top.as<Rec>() : nullptr;
   s->fargs.out_top = s->args.out_top;
   if (hipEventCreate(&s->ev0) != hipSuccess || hipEventCreate(&s->ev1) != hipSuccess ||
       hipEventCreateWithFlags(&s->done, hipEventDisableTiming) != hipSuccess)
@@ -398,16 +406,19 @@ static int sweep_alloc_workspace(bote_sweep* s) {
 }
 
 // bote_sweep_create_keys and, with `is_pinned`, bote_sweep_create_pinned
+// and, with `cons`, bote_sweep_create_constrained (n_con may be 0)
 static int sweep_create(const bote_planet* p, const uint32_t* servers, uint32_t ns, const uint32_t* clients,
                         uint32_t nc, uint32_t n, const bote_objective* objs, uint32_t n_obj, uint32_t K,
                         const bote_ranking_params* rp, int digest, int kernel, uint32_t keys, bool is_pinned,
-                        const uint32_t* pinned, uint32_t n_pinned, bote_sweep** out) {
+                        const uint32_t* pinned, uint32_t n_pinned, bote_sweep** out,
+                        const bote_constraint* cons = nullptr, uint32_t n_con = 0) {
   DevGuard dev_guard;  // the caller's current device is restored on return
   int rc;
   bool has_score = false;
   if (!out) return fail(BOTE_E_ARG, "out is null");
   ARG_TRY(check_sweep_args(p ? p->R : 0, servers, ns, clients, nc, n, objs, n_obj, K, rp, kernel, keys, has_score));
   if (is_pinned) ARG_TRY(check_pinned_args(ns, n, pinned, n_pinned, kernel, keys));
+  ARG_TRY(check_constraint_args(nc, n, cons, n_con, n_obj, kernel, keys));
   HIP_TRY(hipSetDevice(p->device));
   auto* s = new bote_sweep();
   auto cleanup = [&](int code) {
@@ -427,7 +438,17 @@ static int sweep_create(const bote_planet* p, const uint32_t* servers, uint32_t 
     std::sort(s->pz.pin, s->pz.pin + n_pinned);
     s->ptotal = pinned_total(ns, n, n_pinned);
   }
-  if ((rc = sweep_upload_lists(s, servers, clients, objs, rp, has_score, digest, keys))) return cleanup(rc);
+  // the key entries: the objectives, then a constrained sweep's constraints
+  std::vector<bote_objective> entries(objs, objs + n_obj);
+  s->n_con = n_con;
+  s->con.n_lists = n_obj;
+  for (uint32_t c = 0; c < n_con; ++c) {
+    entries.push_back(bote_objective{cons[c].kind, cons[c].slot});
+    s->con.bound[n_obj + c] = cons[c].max_key;
+  }
+  if ((rc = sweep_upload_lists(s, servers, clients, entries.data(), (uint32_t)entries.size(), rp, has_score, digest,
+                               keys)))
+    return cleanup(rc);
   const bool fair = has_score && rp && rp->min_fairness_fpaxos_improv != 0.0;
   if ((rc = sweep_plan_fast(s, servers, clients, fair, kernel))) return cleanup(rc);
   if ((rc = sweep_alloc_workspace(s))) return cleanup(rc);
@@ -439,6 +460,14 @@ int bote_sweep_create_keys(const bote_planet* p, const uint32_t* servers, uint32
                            uint32_t nc, uint32_t n, const bote_objective* objs, uint32_t n_obj, uint32_t K,
                            const bote_ranking_params* rp, int digest, int kernel, uint32_t keys, bote_sweep** out) {
   return sweep_create(p, servers, ns, clients, nc, n, objs, n_obj, K, rp, digest, kernel, keys, false, nullptr, 0, out);
+}
+
+int bote_sweep_create_constrained(const bote_planet* p, const uint32_t* servers, uint32_t ns, const uint32_t* clients,
+                                  uint32_t nc, uint32_t n, const bote_objective* objs, uint32_t n_obj,
+                                  const bote_constraint* cons, uint32_t n_con, uint32_t K,
+                                  const bote_ranking_params* rp, int digest, int kernel, bote_sweep** out) {
+  return sweep_create(p, servers, ns, clients, nc, n, objs, n_obj, K, rp, digest, kernel, 0, false, nullptr, 0, out,
+                      cons, n_con);
 }
 
 int bote_sweep_create_pinned(const bote_planet* p, const uint32_t* servers, uint32_t ns, const uint32_t* clients,
@@ -623,9 +652,18 @@ static int timing_slot(bote_sweep* s, hipEvent_t*& e0, hipEvent_t*& e1) {
   return BOTE_OK;
 }
 
+// a constrained sweep's ConArgs with the counter s->admitted[adm]
+static bote::ConArgs con_args(const bote_sweep* s, int adm) {
+  bote::ConArgs z = s->con;
+  z.admitted = s->admitted.as<unsigned long long>() + adm;
+  return z;
+}
+
 // The generic kernel's top-K launch with `a` on the sweep's grid (a pinned
 // sweep: its pinned variant, [a.rb, a.re) being pinned ranks)
-static hipError_t launch_sweep_eval(const bote_sweep* s, const EvalArgs& a, hipStream_t st) {
+// (a constrained sweep: its constrained variant, counting into s->admitted[adm])
+static hipError_t launch_sweep_eval(const bote_sweep* s, const EvalArgs& a, hipStream_t st, int adm = 0) {
+  if (s->n_con) return bote::launch_eval_con(a, s->n, con_args(s, adm), s->grid, s->bd, s->shm, st);
   return bote::launch_eval(a, s->n, false, s->grid, s->bd, s->shm, st, s->pz.pin_n ? &s->pz : nullptr);
 }
 
@@ -636,6 +674,7 @@ static int launch_generic(bote_sweep* s, uint64_t rb, uint64_t re, hipStream_t s
   a.re = re;
   a.runlen = sweep_runlen(re - rb, s->grid, s->bd);
   HIP_TRY(hipMemsetAsync(s->counters.p, 0, 16, st));
+  if (s->n_con) HIP_TRY(hipMemsetAsync(s->admitted.p, 0, 16, st));
   hipEvent_t *e0 = nullptr, *e1 = nullptr;
   int rc;
   if (timed && (rc = timing_slot(s, e0, e1))) return rc;
@@ -723,6 +762,7 @@ static int launch_fast_path(bote_sweep* s, uint64_t rb, uint64_t re, hipStream_t
   }
   HIP_TRY(bote::launch_zero_ctl(s->counters.as<unsigned long long>(), s->qcount.as<unsigned long long>(),
                                 f.nwchunks ? f.wctr : nullptr, s->counters_alt.as<unsigned long long>(), f.kbound, st));
+  if (s->n_con) HIP_TRY(hipMemsetAsync(s->admitted.p, 0, 16, st));
   // top-K seed: one step of 64 configs per wave at evenly spaced ranks, then
   // per objective the K-th least of the chunks' minimum keys (a bound on the
   // range's K-th key: K distinct configs of the range reach it), so that the
@@ -742,6 +782,7 @@ static int launch_fast_path(bote_sweep* s, uint64_t rb, uint64_t re, hipStream_t
   s->last0 = *e0;
   s->last1 = *e1;
   if (group) HIP_TRY(bote::launch_group(f, s->n, s->def_obj, s->fgrid, s->fshm, st, *e0, *e1));
+  else if (s->n_con) HIP_TRY(bote::launch_fast_con(f, s->n, s->tail, con_args(s, 0), s->fgrid, s->fshm, st, *e0, *e1));
   else HIP_TRY(bote::launch_fast(f, s->n, s->tail, s->pz.pin_n ? &s->pz : nullptr, s->fgrid, s->fshm, st, *e0, *e1));
   // exact fixup of the deferred configs: generic kernel over the rank list
   EvalArgs a = s->args;
@@ -750,8 +791,10 @@ static int launch_fast_path(bote_sweep* s, uint64_t rb, uint64_t re, hipStream_t
   a.rb = 0;
   a.re = QUEUE_CAP;
   a.runlen = 1;
-  a.out_top = s->n_obj ? s->top.as<Rec>() + (size_t)s->fgrid * s->n_obj * bote::KP : nullptr;
-  HIP_TRY(bote::launch_eval(a, s->n, false, s->xgrid, s->bd, s->shm, st));
+  a.out_top = s->n_obj || s->n_con ? s->top.as<Rec>() + (size_t)s->fgrid * s->n_obj * bote::KP : nullptr;
+  // (a constrained sweep: the deferred configs are admitted or rejected here, and counted with the fast kernel's)
+  if (s->n_con) HIP_TRY(bote::launch_eval_con(a, s->n, con_args(s, 0), s->xgrid, s->bd, s->shm, st));
+  else HIP_TRY(bote::launch_eval(a, s->n, false, s->xgrid, s->bd, s->shm, st));
   // overflow fallback: more deferred configs than the queue holds => the
   // generic kernel recomputes the whole range into its own lists/counters and
   // the merge picks those.  Decided on the device (every block of the fallback
@@ -760,11 +803,13 @@ static int launch_fast_path(bote_sweep* s, uint64_t rb, uint64_t re, hipStream_t
   g.rb = rb;
   g.re = re;
   g.runlen = sweep_runlen(re - rb, s->grid, s->bd);
-  g.out_top = s->n_obj ? s->top_alt.as<Rec>() : nullptr;
+  g.out_top = s->n_obj || s->n_con ? s->top_alt.as<Rec>() : nullptr;
   g.out_counters = s->counters_alt.as<unsigned long long>();
   g.run_if_over = s->qcount.as<unsigned long long>();
   g.over_cap = QUEUE_CAP;
-  HIP_TRY(launch_sweep_eval(s, g, st));
+  // (a constrained sweep: the fallback counts the whole range into a counter
+  // of its own, which bote_sweep_admitted reads in place of the first)
+  HIP_TRY(launch_sweep_eval(s, g, st, 1));
   return merge_chain(s, s->fgrid + s->xgrid, st, s->qcount.as<unsigned long long>(), s->grid, f.kbound);
 }
 
@@ -887,6 +932,25 @@ int bote_sweep_deferred(bote_sweep* s, void* hip_stream, uint64_t* out) {
   HIP_TRY(hipMemcpyAsync(&q, s->qcount.p, 8, hipMemcpyDeviceToHost, (hipStream_t)hip_stream));
   HIP_TRY(hipStreamSynchronize((hipStream_t)hip_stream));
   *out = q;
+  return BOTE_OK;
+}
+
+int bote_sweep_admitted(bote_sweep* s, void* hip_stream, uint64_t* out) {
+  DevGuard dev_guard;  // the caller's current device is restored on return
+  if (!s || !out) return fail(BOTE_E_ARG, "null argument");
+  *out = 0;
+  if (!s->launched) return fail(BOTE_E_ARG, "sweep not launched");
+  if (!s->n_con) {
+    *out = s->last_re - s->last_rb;
+    return BOTE_OK;
+  }
+  HIP_TRY(hipSetDevice(s->p->device));
+  unsigned long long q = 0, adm[2] = {0, 0};
+  if (s->path != Path::Generic)
+    HIP_TRY(hipMemcpyAsync(&q, s->qcount.p, 8, hipMemcpyDeviceToHost, (hipStream_t)hip_stream));
+  HIP_TRY(hipMemcpyAsync(adm, s->admitted.p, 16, hipMemcpyDeviceToHost, (hipStream_t)hip_stream));
+  HIP_TRY(hipStreamSynchronize((hipStream_t)hip_stream));
+  *out = q > QUEUE_CAP ? adm[1] : adm[0];  // (the merge's own choice of the fallback's lists)
   return BOTE_OK;
 }
 

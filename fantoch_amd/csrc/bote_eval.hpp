@@ -856,9 +856,17 @@ __device__ __forceinline__ CensusLds census_lds(const Smem& s) {
 // launcher sizes it so): the thresholds take the lists' region (tk.top, at
 // least n_obj x KP records), the bins the candidate buffer's (tk.cand, 16 B per
 // thread of the block).
-template <int N, bool FULL, bool X, int PASSES = EVAL_PLAIN, bool PIN = false, bool CENSUS = false>
+// CON: the constrained variant (ConArgs, bote_kernels.hpp; base key set, ranks
+// or the deferred rank list, unpinned): a.n_obj key entries, the objectives and
+// then the constraints, built alike; a config whose trailing keys are not all
+// within their bounds offers nothing, the others are counted (con_admit).  The
+// lists are the first n_lists entries'.  The valid count and the digest are the
+// unconstrained sweep's.
+template <int N, bool FULL, bool X, int PASSES = EVAL_PLAIN, bool PIN = false, bool CENSUS = false, bool CON = false>
 __global__ void __launch_bounds__(256)
-    eval_kernel(std::conditional_t<CENSUS, CensusEvalArgs, std::conditional_t<PIN, PinEvalArgs, EvalArgs>> a) {
+    eval_kernel(std::conditional_t<CON, ConEvalArgs,
+                                   std::conditional_t<CENSUS, CensusEvalArgs, std::conditional_t<PIN, PinEvalArgs, EvalArgs>>> a) {
+  static_assert(!CON || (!FULL && !X && !PIN && !CENSUS), "the constrained variant is an unpinned top-K sweep of the base key set");
   static_assert(!PIN || (!FULL && !X), "the pinned variant is a top-K sweep of the base key set");
   static_assert(!CENSUS || (!FULL && !X && !PIN), "the census variant sweeps ranks of the base key set");
   static_assert(CENSUS_T <= KP && CENSUS_T * 8 * MAXOBJ <= 256 * 16, "the census sink fits the top-K regions it takes");
@@ -879,13 +887,17 @@ __global__ void __launch_bounds__(256)
     // the deferred-config fix-up with nothing deferred (the common case):
     // empty lists for the merge, nothing staged (block-uniform)
     if (topk && !CENSUS) {
-      Rec* dst = a.out_top + (size_t)blockIdx.x * a.n_obj * KP;
-      for (uint32_t i = tid; i < (uint32_t)a.n_obj * KP; i += BD) dst[i] = rec_max();
+      Rec* dst = a.out_top + (size_t)blockIdx.x * list_count<CON>(a) * KP;
+      for (uint32_t i = tid; i < (uint32_t)list_count<CON>(a) * KP; i += BD) dst[i] = rec_max();
     }
     return;
   }
   if constexpr (CENSUS) census_init(census_lds(s), nullptr, a.cz, a.n_obj, a.obj_kind);  // (published by the stage's barriers)
   stage_planet<N>(a, s, Cursor::unranks(a), topk && !CENSUS);
+  if constexpr (CON) {
+    if (topk) con_init(s.tk, a.cz);
+    __syncthreads();
+  }
 
   const uint64_t total = Cursor::total(a), runlen = Cursor::runlen(a);
   const uint64_t njobs = (total + runlen - 1) / runlen;
@@ -893,6 +905,7 @@ __global__ void __launch_bounds__(256)
   const uint64_t outer = (njobs + G - 1) / G;
   const bool sorted_in = Cursor::sorted_in(a);
   uint64_t valid_cnt = 0, digest = 0;
+  [[maybe_unused]] std::conditional_t<CON, uint64_t, char> adm_cnt{};  // CON: the lane's admitted configs
 
   for (uint64_t it = 0; it < outer; ++it) {
     const uint64_t job = it * G + (uint64_t)blockIdx.x * BD + tid;
@@ -950,8 +963,11 @@ __global__ void __launch_bounds__(256)
             }
           }
         }
+        if constexpr (CON) {
+          if (have && con_admit(s.tk, list_count<CON>(a), a.n_obj, key, ok)) ++adm_cnt;
+        }
         if constexpr (CENSUS) census_step(census_lds(s), a.n_obj, a.cz.T, key, ok, frank);
-        else topk_step(s.tk, a.n_obj, a.K, key, ok, frank);
+        else topk_step(s.tk, list_count<CON>(a), a.K, key, ok, frank);
       }
       Cursor::next(a, have, p, q, rank);
     }
@@ -961,13 +977,16 @@ __global__ void __launch_bounds__(256)
     if (valid_cnt) atomicAdd(&a.out_counters[0], (unsigned long long)valid_cnt);
     if (digest) atomicAdd(&a.out_counters[1], (unsigned long long)digest);
   }
+  if constexpr (CON) {
+    if (adm_cnt) atomicAdd(a.cz.admitted, (unsigned long long)adm_cnt);
+  }
   if constexpr (CENSUS) {
     __syncthreads();
     census_flush(census_lds(s), a.cz, a.n_obj);
   } else if (topk) {
     __syncthreads();
-    Rec* dst = a.out_top + (size_t)blockIdx.x * a.n_obj * KP;
-    for (uint32_t i = tid; i < (uint32_t)a.n_obj * KP; i += BD) dst[i] = s.tk.top[i];
+    Rec* dst = a.out_top + (size_t)blockIdx.x * list_count<CON>(a) * KP;
+    for (uint32_t i = tid; i < (uint32_t)list_count<CON>(a) * KP; i += BD) dst[i] = s.tk.top[i];
   }
 }
 
@@ -985,5 +1004,6 @@ BOTE_HIDDEN const void* eval_fn_pctl(uint32_t n, bool keys);    // bote_eval_pct
 BOTE_HIDDEN const void* eval_fn_mdtm(uint32_t n, bool keys);    // bote_eval_mdtm.hip: top-K, EVAL_MDTM
 BOTE_HIDDEN const void* eval_fn_pinned(uint32_t n, bool passes);  // bote_eval_pinned.hip: EVAL_MDTM (passes) or EVAL_PLAIN
 BOTE_HIDDEN const void* eval_fn_census(uint32_t n, bool passes);  // bote_eval_census.hip: the same two, census sink
+BOTE_HIDDEN const void* eval_fn_con(uint32_t n, bool passes);     // bote_eval_con.hip: the same two, constrained
 
 }  // namespace bote

@@ -705,6 +705,44 @@ Status check_sweep_args(uint32_t R, const uint32_t* servers, uint32_t ns, const 
   return OK;
 }
 
+Status check_constraint_args(uint32_t nc, uint32_t n, const bote_constraint* cons, uint32_t n_con, uint32_t n_obj,
+                             int kernel, uint32_t keys) {
+  if (n_con && !cons) return fail(BOTE_E_ARG, "constraints null");
+  for (uint32_t c = 0; c < n_con; ++c) {
+    const bool pctl = is_percentile_kind(cons[c].kind);
+    if (cons[c].kind > BOTE_OBJ_COV && cons[c].kind != BOTE_OBJ_MAX && cons[c].kind != BOTE_OBJ_MDTM && !pctl)
+      return fail(BOTE_E_ARG, "unknown constraint kind");
+    if (cons[c].kind == BOTE_OBJ_SCORE) return fail(BOTE_E_ARG, "SCORE is not a constraint kind");
+    if (cons[c].slot >= (keys ? BOTE_NSLOTS_X : BOTE_NSLOTS)) return fail(BOTE_E_ARG, "constraint slot out of range");
+    if (!slot_exists_n(n, cons[c].slot, keys))
+      return fail(BOTE_E_ARG, "constraint slot does not exist for this n (max_f < 2)");
+    if (pctl && percentile_need(cons[c].kind & 0xFFFF, slot_count(cons[c].slot, nc, n)) > PCTL_MAX_NEED)
+      return fail(BOTE_E_RANGE, "percentile constraint needs more than 8 of the slot's largest values");
+  }
+  if ((uint64_t)n_obj + n_con > BOTE_MAX_OBJECTIVES)
+    return fail(BOTE_E_RANGE, "more than 8 objectives and constraints");
+  if (n_con && keys) return fail(BOTE_E_ARG, "constrained sweeps compute the base key set");
+  if (n_con && kernel == BOTE_KERNEL_GROUP)
+    return fail(BOTE_E_ARG, "the group kernel does not apply constraints (fast or generic kernel)");
+  return OK;
+}
+
+TailPlan fast_tail_plan(const uint32_t* dev_kinds, uint32_t n_keys) {
+  TailPlan t;
+  bool mdtm = false;
+  for (uint32_t o = 0; o < n_keys; ++o) {
+    if (dev_kinds[o] == BOTE_OBJ_MAX) t.tail = std::max(t.tail, (int)TAIL_MAX);
+    if (dev_kinds[o] >= DEV_KIND_PCTL) {
+      t.tail = TAIL_LIST;
+      t.need = std::max(t.need, dev_kinds[o] & DEV_PCTL_NEED_MASK);
+    }
+    mdtm = mdtm || dev_kinds[o] == BOTE_OBJ_MDTM;
+  }
+  t.mixed = mdtm && t.tail != TAIL_PLAIN;
+  if (mdtm) t.tail = TAIL_MDTM;
+  return t;
+}
+
 Status check_pinned_args(uint32_t ns, uint32_t n, const uint32_t* pinned, uint32_t n_pinned, int kernel,
                          uint32_t keys) {
   if (!pinned || n_pinned == 0) return fail(BOTE_E_ARG, "pinned list is null or empty");

@@ -262,6 +262,29 @@ Status check_leaderless_args(uint32_t R, const uint32_t* servers, uint32_t ns, c
 Status check_sweep_args(uint32_t R, const uint32_t* servers, uint32_t ns, const uint32_t* clients, uint32_t nc,
                         uint32_t n, const bote_objective* objs, uint32_t n_obj, uint32_t K,
                         const bote_ranking_params* rp, int kernel, uint32_t keys, bool& has_score);
+// bote_sweep_create_constrained, after check_sweep_args.  In order: a null list
+// with n_con > 0; then per constraint an unknown kind, the SCORE kind (not a
+// constraint), its slot's range and existence for n and, for a percentile, the
+// PCTL_MAX_NEED values (BOTE_E_RANGE, as for objectives); then n_obj + n_con
+// above BOTE_MAX_OBJECTIVES (BOTE_E_RANGE); then, with n_con > 0, the extended
+// key set and a forced group kernel (neither applies constraints).
+Status check_constraint_args(uint32_t nc, uint32_t n, const bote_constraint* cons, uint32_t n_con, uint32_t n_obj,
+                             int kernel, uint32_t keys);
+// The fast kernel's variant for a sweep's key entries, its objectives and its
+// constraints alike (kinds as the kernels take them, a percentile with its need:
+// bote_kernels.hpp OBJ_PCTL): a MAX entry means maxima (TAIL_MAX), a percentile
+// lists (TAIL_LIST, which serve a MAX too; `need` is the deepest one's), an MDTM
+// entry the MDTM variant (TAIL_MDTM), which carries neither: `mixed` when it
+// stands beside a MAX or a percentile (the generic kernel then).  The values
+// are bote::FAST_*.
+enum { TAIL_PLAIN = 0, TAIL_MAX = 1, TAIL_LIST = 2, TAIL_MDTM = 3 };
+constexpr uint32_t DEV_KIND_PCTL = 0x10000u, DEV_PCTL_NEED_MASK = 15u;
+struct TailPlan {
+  int tail = TAIL_PLAIN;
+  uint32_t need = 0;
+  bool mixed = false;
+};
+TailPlan fast_tail_plan(const uint32_t* dev_kinds, uint32_t n_keys);
 // bote_sweep_create_pinned, after check_sweep_args.  In order: a null or empty
 // pinned list, n_pinned >= n, a position >= ns, a repeated position, a forced
 // group kernel (it does not sweep pinned members), the extended key set (the

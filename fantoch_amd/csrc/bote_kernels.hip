@@ -127,7 +127,10 @@ size_t eval_smem_bytes(const EvalArgs& a, uint32_t n, uint32_t bd, bool topk) {
 // the passes of the ones below it)
 // `census`: the census variant (bote_census.hpp; base keys, unpinned): EVAL_PLAIN,
 // or EVAL_MDTM for a census with a MAX, percentile or MDTM objective
-static const void* eval_fn(uint32_t n, bool full, bool keys, int passes, bool pin, bool census = false) {
+// `con`: the constrained variant (base keys, unpinned, top-K): the same two
+static const void* eval_fn(uint32_t n, bool full, bool keys, int passes, bool pin, bool census = false,
+                           bool con = false) {
+  if (con) return full || keys || pin || census ? nullptr : eval_fn_con(n, passes != EVAL_PLAIN);
   if (census) return full || keys || pin ? nullptr : eval_fn_census(n, passes != EVAL_PLAIN);
   if (pin) return full || keys ? nullptr : eval_fn_pinned(n, passes != EVAL_PLAIN);
   if (full) return eval_fn_full(n, keys);
@@ -136,8 +139,9 @@ static const void* eval_fn(uint32_t n, bool full, bool keys, int passes, bool pi
   return eval_fn_topk(n, keys);
 }
 
-int eval_occupancy(uint32_t n, bool full, uint32_t bd, size_t shm, bool keys, int passes, bool pin, bool census) {
-  const void* k = eval_fn(n, full, keys, passes, pin, census);
+int eval_occupancy(uint32_t n, bool full, uint32_t bd, size_t shm, bool keys, int passes, bool pin, bool census,
+                   bool con) {
+  const void* k = eval_fn(n, full, keys, passes, pin, census, con);
   return k ? kernel_occupancy(k, bd, shm, 1) : 0;
 }
 
@@ -152,6 +156,16 @@ hipError_t launch_eval(const EvalArgs& a, uint32_t n, bool full, uint32_t grid, 
   static_cast<EvalArgs&>(pa) = a;
   pa.pz = *pin;
   return launch_kernel(k, pa, grid, bd, shm, st);
+}
+
+hipError_t launch_eval_con(const EvalArgs& a, uint32_t n, const ConArgs& z, uint32_t grid, uint32_t bd, size_t shm,
+                           hipStream_t st) {
+  const void* k = eval_fn(n, false, a.keys != 0, eval_passes(a.obj_kind, a.n_obj), false, false, true);
+  if (!k || a.cfgs || !z.admitted || a.n_obj > MAXOBJ || z.n_lists > (uint32_t)a.n_obj) return hipErrorInvalidValue;
+  ConEvalArgs ca{};
+  static_cast<EvalArgs&>(ca) = a;
+  ca.cz = z;
+  return launch_kernel(k, ca, grid, bd, shm, st);
 }
 
 hipError_t launch_eval_census(const EvalArgs& a, uint32_t n, const CensusArgs& z, uint32_t grid, uint32_t bd,

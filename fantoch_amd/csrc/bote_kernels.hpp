@@ -238,6 +238,57 @@ struct CensusArgs {
   uint32_t T;                 // 1 .. CENSUS_T
   unsigned long long* below;  // [n_obj][T]: += the configs before each threshold
 };
+// A constrained sweep (DESIGN.md §4 "Constrained sweeps"): the launch's key
+// entries [0, n_lists) are its objectives, the entries [n_lists, n_obj) of
+// obj_kind / obj_slot its constraints, whose keys the kernels build like any
+// objective's.  A config is admitted when key[o] <= bound[o] for every
+// constraint entry o; only an admitted config offers its keys to the lists, and
+// the admitted configs are counted into *admitted.  The constrained variants of
+// the fast and the generic kernel take it at the end of their arguments; they
+// size their LDS for n_obj lists and write, merge and dump n_lists.
+struct ConArgs {
+  uint32_t n_lists;
+  uint64_t bound[MAXOBJ];         // by key entry; read from n_lists on
+  unsigned long long* admitted;   // += the admitted configs of the launch
+};
+// the kernels' arguments with it at the end (the kernarg offsets of FastArgs and EvalArgs stay)
+struct ConFastArgs : FastArgs {
+  ConArgs cz;
+};
+struct ConEvalArgs : EvalArgs {
+  ConArgs cz;
+};
+// Where the constrained variants keep the bounds: both kernels' block top-K has
+// MAXOBJ threshold records (TopkLds::thr) and touches only those of its lists,
+// so the rank word of record o >= n_lists holds bound[o] (its key word stays
+// all ones, "no threshold", for the key builders that screen against it).  The
+// bounds are read back per config from LDS, not kept in registers.
+#ifdef __HIPCC__
+// the entries that have a list: all of them, or a constrained variant's first n_lists (read where
+// it is used, as a.n_obj is: the other instantiations keep their code)
+template <bool CON, class Args>
+__device__ __forceinline__ int list_count(const Args& a) {
+  if constexpr (CON) return (int)a.cz.n_lists;
+  else return a.n_obj;
+}
+// every thread of the block, after topk_init and its barrier; the caller's next barrier publishes the bounds
+__device__ __forceinline__ void con_init(const TopkLds& t, const ConArgs& z) {
+  if (threadIdx.x < (uint32_t)MAXOBJ && threadIdx.x >= z.n_lists) t.thr[threadIdx.x].rank = z.bound[threadIdx.x];
+}
+// An evaluated config's verdict, from its n_keys keys: admitted when every
+// constraint key was built and lies within its bound (inclusive); a rejected
+// config withdraws every offer.
+__device__ __forceinline__ bool con_admit(const TopkLds& t, int n_lists, int n_keys, const uint64_t (&key)[MAXOBJ],
+                                          bool (&ok)[MAXOBJ]) {
+  bool adm = true;
+#pragma unroll
+  for (int o = 0; o < MAXOBJ; ++o)
+    if (o >= n_lists && o < n_keys) adm = adm && ok[o] && key[o] <= t.thr[o].rank;
+#pragma unroll
+  for (int o = 0; o < MAXOBJ; ++o) ok[o] = ok[o] && adm;
+  return adm;
+}
+#endif
 #ifdef BOTE_DEBUG
 // bit `code` of *dbg_flag when `cond` fails (codes: DESIGN.md §5, debug build)
 #define GASSERT(a, cond, code)                                                    \
@@ -278,7 +329,9 @@ enum { FAST_PLAIN = 0, FAST_MAX = 1, FAST_LIST = 2, FAST_MDTM = 3 };
 // (census: the census variant, FAST_PLAIN and unpinned: thresholds and bins in place of the lists)
 size_t fast_smem_bytes(const FastArgs& a, uint32_t n, int tail, bool census = false);
 // (pin: PIN_*; the pinned and the batch variant are FAST_PLAIN only: SCORE, MEAN and COV objectives)
-int fast_occupancy(uint32_t n, int tail, int pin, size_t shm, bool census = false);
+// (con: the constrained variant, unpinned; fast_has_constrained: whether it is built for `tail`)
+int fast_occupancy(uint32_t n, int tail, int pin, size_t shm, bool census = false, bool con = false);
+bool fast_has_constrained(uint32_t n, int tail);
 // (e0, e1: events carried by the dispatch itself, bote_launch.hpp, for a timed launch)
 hipError_t launch_fast(const FastArgs& a, uint32_t n, int tail, const PinArgs* pin, uint32_t grid, size_t shm,
                        hipStream_t st, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
@@ -289,6 +342,10 @@ hipError_t launch_fast_batch(const FastArgs& a, uint32_t n, const BatchArgs& b, 
 // and the deferred queue; a.out_top and a.K are not read
 hipError_t launch_fast_census(const FastArgs& a, uint32_t n, const CensusArgs& z, uint32_t grid, size_t shm,
                               hipStream_t st, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
+// the constrained variant (unpinned) over [a.rb, a.re): a.n_obj counts the objectives and the
+// constraints, z.n_lists lists per block go to a.out_top
+hipError_t launch_fast_con(const FastArgs& a, uint32_t n, int tail, const ConArgs& z, uint32_t grid, size_t shm,
+                           hipStream_t st, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
 size_t group_smem_bytes(const FastArgs& a, uint32_t n);
 bool group_uses_lines(uint32_t n);  // n <= 7: client lines (FastArgs::gslots) and register lookups
 // the extended key set's group kernels target BOTE_GROUP_WAVES_XK waves per
@@ -327,7 +384,7 @@ inline int eval_passes(const uint32_t* obj_kind, int n_obj) {
 // sweep's overflow fallback, and MAX / percentile / MDTM objectives.  It has
 // EVAL_PLAIN and EVAL_MDTM; a percentile sweep takes EVAL_MDTM)
 int eval_occupancy(uint32_t n, bool full, uint32_t bd, size_t shm, bool keys = false, int passes = EVAL_PLAIN,
-                   bool pin = false, bool census = false);
+                   bool pin = false, bool census = false, bool con = false);
 hipError_t launch_eval(const EvalArgs& a, uint32_t n, bool full, uint32_t grid, uint32_t bd, size_t shm,
                        hipStream_t st, const PinArgs* pin = nullptr);
 // The census variant (base keys; EVAL_PLAIN, or EVAL_MDTM for a MAX, percentile
@@ -337,6 +394,12 @@ hipError_t launch_eval(const EvalArgs& a, uint32_t n, bool full, uint32_t grid, 
 // a.rb (the queue overflowed: the fallback counts the range) it counts nothing.
 hipError_t launch_eval_census(const EvalArgs& a, uint32_t n, const CensusArgs& z, uint32_t grid, uint32_t bd,
                               size_t shm, hipStream_t st, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
+// The constrained variant (base keys, unpinned, top-K; EVAL_PLAIN, or EVAL_MDTM
+// for a percentile or MDTM entry) over the ranks [a.rb, a.re) or the rank list:
+// a.n_obj counts the objectives and the constraints, shm is sized for that many
+// lists, and z.n_lists lists per block go to a.out_top
+hipError_t launch_eval_con(const EvalArgs& a, uint32_t n, const ConArgs& z, uint32_t grid, uint32_t bd, size_t shm,
+                           hipStream_t st);
 // A census launch's start: the n = n_obj x T thresholds (host memory, read before
 // the call returns) into the device table thr, and below[0 .. n), counters[0 .. 1]
 // and, where given, below_alt, counters_alt and *qcount zeroed

@@ -28,6 +28,10 @@
 // which is the sequence of the stages; the launcher.  What a variant FAST_*
 // adds to a config is in its tail carrier (bote_fast_tail.hpp), which has one
 // hook per stage.
+//
+// The constrained variant's instantiations are a unit of their own
+// (bote_sweep_con.hip, which defines BOTE_FAST_CON_UNIT and includes this
+// file): it compiles beside this one and leaves out what is not a template.
 #include "bote_census.hpp"
 #include "bote_fast_tail.hpp"
 #include "bote_launch.hpp"
@@ -84,6 +88,7 @@ constexpr int BATCH_LIM_WORD = 10;
 static_assert(1 + MAXOBJ <= BATCH_LIM_WORD && (BATCH_LIM_WORD + 2) * 4 <= 48 && BATCH_LIM_WORD % 2 == 0,
               "the limits follow the top-K counters inside the reserved 48 bytes, 8-byte aligned");
 
+#ifndef BOTE_FAST_CON_UNIT
 size_t fast_smem_bytes(const FastArgs& a, uint32_t n, int tail, bool census) {
   int nl = 0;
   switch (n) {
@@ -95,6 +100,7 @@ size_t fast_smem_bytes(const FastArgs& a, uint32_t n, int tail, bool census) {
   }
   return fast_layout(a, (int)n, nl <= 2 ? 1 : 2, tail, census).total;
 }
+#endif
 
 struct FastSmem {
   unsigned char* base;  // dynamic LDS base; byte offsets below are relative to it
@@ -542,10 +548,19 @@ __device__ __forceinline__ void colocated(const unsigned char* B, const Leader& 
 // and a flush of counts in place of the list dump.  A deferred config offers
 // no key (ok[] stays false), so it is counted for no objective here and for
 // every one by the generic kernel's census variant over the queue.
-template <int N, int TAIL, int PIN = PIN_NONE, bool CENSUS = false>
+// CON (unpinned; ConArgs, bote_kernels.hpp): the constrained variant.  The
+// launch's key entries are its objectives, then its constraints; the stages
+// build every entry's key alike.  After finish_config the trailing keys are
+// compared with their bounds (con_admit): a rejected config withdraws its
+// offers, an admitted one is counted.  A deferred config is neither: the
+// generic kernel's constrained variant decides it over the queue.  The block
+// top-K, the list dump and the merges see the first n_lists entries only.
+template <int N, int TAIL, int PIN = PIN_NONE, bool CENSUS = false, bool CON = false>
 __global__ void __launch_bounds__(FAST_BD, 4)
-    sweep_fast_kernel(std::conditional_t<CENSUS, CensusFastArgs, typename Members<N, PIN>::Args> a) {
+    sweep_fast_kernel(std::conditional_t<CON, ConFastArgs,
+                                         std::conditional_t<CENSUS, CensusFastArgs, typename Members<N, PIN>::Args>> a) {
   using TL = Tail<N, TAIL>;
+  static_assert(!CON || (PIN == PIN_NONE && !CENSUS), "the constrained variant is an unpinned top-K sweep");
   static_assert(PIN == PIN_NONE || TL::plain, "the pinned variants compute SCORE, MEAN and COV objectives");
   static_assert(!CENSUS || (PIN == PIN_NONE && TL::plain), "the census variant is unpinned and computes SCORE, MEAN and COV objectives");
   constexpr bool BATCH = PIN == PIN_BATCH;
@@ -557,6 +572,7 @@ __global__ void __launch_bounds__(FAST_BD, 4)
 
   stage_lds<N, CENSUS>(a, s, tid);
   if constexpr (CENSUS) census_init(s.cl, s.tk.thr, a.cz, a.n_obj, a.obj_kind);  // (published by the next stage's barrier)
+  if constexpr (CON) con_init(s.tk, a.cz);  // (after stage_lds' barrier; published by the next stage's)
   position_sums<TL>(a, s, tid);
 
   const uint32_t cstride = a.cq_stride * 8;  // bytes per CQT column
@@ -574,7 +590,7 @@ __global__ void __launch_bounds__(FAST_BD, 4)
     if constexpr (PIN == PIN_ONE) return a.pz;
     else return zb;
   }();
-  Rec* dst = a.out_top + (size_t)blockIdx.x * a.n_obj * KP;
+  Rec* dst = a.out_top + (size_t)blockIdx.x * list_count<CON>(a) * KP;
   unsigned long long* counters = a.out_counters;
   if constexpr (BATCH) {
     if (unit >= a.bz.n_sets * a.bz.slices) return;  // (the launcher's grid is at most the units)
@@ -607,6 +623,7 @@ __global__ void __launch_bounds__(FAST_BD, 4)
     const uint64_t njobs = (total + runlen - 1) / runlen;
     const uint64_t outer = (njobs + G - 1) / G;
     uint64_t valid_cnt = 0, digest = 0;
+    [[maybe_unused]] Only<CON, uint64_t> adm_cnt{};  // CON: the lane's admitted configs
 
     for (uint64_t it = 0; it < outer; ++it) {
       const uint64_t job = it * G + first;
@@ -663,10 +680,13 @@ __global__ void __launch_bounds__(FAST_BD, 4)
               have = false;
               TL::withdraw(ok);
             }
+            if constexpr (CON) {
+              if (have && con_admit(s.tk, list_count<CON>(a), a.n_obj, key, ok)) ++adm_cnt;
+            }
           }
         }
         if constexpr (CENSUS) census_step(s.cl, a.n_obj, a.cz.T, key, ok, frank);
-        else if (!ABLATE(a, 4)) topk_step(s.tk, a.n_obj, a.K, key, ok, frank);
+        else if (!ABLATE(a, 4)) topk_step(s.tk, list_count<CON>(a), a.K, key, ok, frank);
         mb.next(a.ns, pz, jobok && rank < re);
         ++rank;
       }
@@ -681,15 +701,36 @@ __global__ void __launch_bounds__(FAST_BD, 4)
     }
     if (valid_cnt) atomicAdd(&counters[0], (unsigned long long)valid_cnt);
     if (digest) atomicAdd(&counters[1], (unsigned long long)digest);
+    if constexpr (CON) {
+      if (adm_cnt) atomicAdd(a.cz.admitted, (unsigned long long)adm_cnt);
+    }
     __syncthreads();
     if constexpr (CENSUS) census_flush(s.cl, a.cz, a.n_obj);
     else
-      for (uint32_t i = tid; i < (uint32_t)a.n_obj * KP; i += FAST_BD) dst[i] = s.tk.top[i];
+      for (uint32_t i = tid; i < (uint32_t)list_count<CON>(a) * KP; i += FAST_BD) dst[i] = s.tk.top[i];
     if constexpr (BATCH) more = (unit += gridDim.x) < a.bz.n_sets * a.bz.slices;
   } while (more);
 }
 
 // ------------------------------------------------------------- launcher ---
+// the constrained variant for config size n (null: not built for `tail`), defined by its own unit
+__attribute__((visibility("hidden"))) const void* fast_fn_con(uint32_t n, int tail);
+#ifdef BOTE_FAST_CON_UNIT
+const void* fast_fn_con(uint32_t n, int tail) {
+  switch (n) {
+#define FN_CASE(NN)                                                                                      \
+  case NN:                                                                                               \
+    return tail == FAST_MDTM   ? (const void*)sweep_fast_kernel<NN, FAST_MDTM, PIN_NONE, false, true>    \
+           : tail == FAST_LIST ? (const void*)sweep_fast_kernel<NN, FAST_LIST, PIN_NONE, false, true>    \
+           : tail == FAST_MAX  ? (const void*)sweep_fast_kernel<NN, FAST_MAX, PIN_NONE, false, true>     \
+                               : (const void*)sweep_fast_kernel<NN, FAST_PLAIN, PIN_NONE, false, true>;
+    FN_CASE(2) FN_CASE(3) FN_CASE(4) FN_CASE(5) FN_CASE(6) FN_CASE(7) FN_CASE(8) FN_CASE(9)
+    FN_CASE(10) FN_CASE(11) FN_CASE(12) FN_CASE(13) FN_CASE(14) FN_CASE(15) FN_CASE(16)
+#undef FN_CASE
+    default: return nullptr;
+  }
+}
+#else
 // the kernel for config size n (null: unsupported; the pinned and the batch
 // variant, pin = PIN_*, are FAST_PLAIN only), for the occupancy query and the
 // launch alike
@@ -714,10 +755,12 @@ static const void* fast_fn(uint32_t n, int tail, int pin, bool census = false) {
   }
 }
 
-int fast_occupancy(uint32_t n, int tail, int pin, size_t shm, bool census) {
-  const void* k = fast_fn(n, tail, pin, census);
+int fast_occupancy(uint32_t n, int tail, int pin, size_t shm, bool census, bool con) {
+  const void* k = con ? (pin == PIN_NONE && !census ? fast_fn_con(n, tail) : nullptr) : fast_fn(n, tail, pin, census);
   return k ? kernel_occupancy(k, FAST_BD, shm, 1) : 0;
 }
+
+bool fast_has_constrained(uint32_t n, int tail) { return fast_fn_con(n, tail) != nullptr; }
 
 hipError_t launch_fast(const FastArgs& a, uint32_t n, int tail, const PinArgs* pin, uint32_t grid, size_t shm,
                        hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
@@ -728,6 +771,16 @@ hipError_t launch_fast(const FastArgs& a, uint32_t n, int tail, const PinArgs* p
   static_cast<FastArgs&>(pa) = a;
   pa.pz = *pin;
   return launch_kernel(k, pa, grid, FAST_BD, shm, st, e0, e1);
+}
+
+hipError_t launch_fast_con(const FastArgs& a, uint32_t n, int tail, const ConArgs& z, uint32_t grid, size_t shm,
+                           hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
+  const void* k = fast_fn_con(n, tail);
+  if (!k || !z.admitted || a.n_obj > MAXOBJ || z.n_lists > (uint32_t)a.n_obj) return hipErrorInvalidValue;
+  ConFastArgs ca{};
+  static_cast<FastArgs&>(ca) = a;
+  ca.cz = z;
+  return launch_kernel(k, ca, grid, FAST_BD, shm, st, e0, e1);
 }
 
 hipError_t launch_fast_census(const FastArgs& a, uint32_t n, const CensusArgs& z, uint32_t grid, size_t shm,
@@ -751,5 +804,6 @@ hipError_t launch_fast_batch(const FastArgs& a, uint32_t n, const BatchArgs& b, 
   ba.bz = b;
   return launch_kernel(k, ba, grid, FAST_BD, shm, st, e0, e1);
 }
+#endif  // BOTE_FAST_CON_UNIT
 
 }  // namespace bote

@@ -133,6 +133,17 @@ typedef struct {
   uint32_t slot; /* BOTE_SLOT_* (ignored for BOTE_OBJ_SCORE) */
 } bote_objective;
 
+/* A constraint of a constrained sweep (bote_sweep_create_constrained): `kind`
+ * and `slot` are an objective's (MEAN, COV, MAX, a percentile or MDTM; not
+ * SCORE), and a config's constraint key is, bit for bit, the key a record of
+ * the objective (kind, slot) carries for it (bote_topk_record).  The config is
+ * admitted iff key <= max_key as unsigned 64-bit integers (inclusive). */
+typedef struct {
+  uint32_t kind; /* BOTE_OBJ_* except BOTE_OBJ_SCORE */
+  uint32_t slot; /* BOTE_SLOT_* */
+  uint64_t max_key;
+} bote_constraint;
+
 /* RankingParams (search.rs:617-649); min_n/max_n are implied by the call. */
 typedef struct {
   double min_mean_fpaxos_improv;
@@ -346,6 +357,32 @@ int bote_sweep_create_pinned(const bote_planet* p, const uint32_t* servers, uint
                              const uint32_t* pinned, uint32_t n_pinned,
                              const bote_objective* objs, uint32_t n_obj, uint32_t K,
                              const bote_ranking_params* rp, int digest, int kernel, bote_sweep** out);
+/* bote_sweep_create_ex over the configs that meet key bounds: "the best X among
+ * the configs that meet Y".  A config is admitted iff every constraint's key
+ * is <= its max_key; only admitted configs are offered to any objective's
+ * list, so the SCORE list holds the configs that are admitted and valid.  The
+ * lists stay in (key, rank) order with full colex ranks: the result block has
+ * the layout of an unconstrained sweep's, and blocks of disjoint rank ranges
+ * merge with bote_merge_device.  The valid count and the digest are NOT
+ * filtered: they are the unconstrained sweep's over the same range.  The
+ * number of admitted configs of a launch is bote_sweep_admitted.  With n_con ==
+ * 0, or every max_key all ones, the result is the plain sweep's.
+ * n_obj + n_con <= BOTE_MAX_OBJECTIVES (BOTE_E_RANGE above); base key set,
+ * unpinned.  Routing is decided over the objectives' and the constraints'
+ * kinds together by bote_sweep_create_ex's rules (a MAX, percentile or MDTM
+ * constraint picks the fast kernel's variant as such an objective does; MDTM
+ * beside MAX or a percentile, or a percentile that needs 5..8 values, runs the
+ * generic kernel, and is BOTE_E_ARG on a forced fast kernel).  The group
+ * kernel does not apply constraints: AUTO with n_con > 0 takes the fast kernel
+ * when eligible, else the generic kernel, and a forced group kernel is
+ * BOTE_E_ARG.  With n_con == 0 it plans exactly as bote_sweep_create_keys with
+ * the base key set does.  Every other bote_sweep_* entry works on the handle
+ * unchanged. */
+int bote_sweep_create_constrained(const bote_planet* p, const uint32_t* servers, uint32_t ns,
+                                  const uint32_t* clients, uint32_t nc, uint32_t n,
+                                  const bote_objective* objs, uint32_t n_obj,
+                                  const bote_constraint* cons, uint32_t n_con, uint32_t K,
+                                  const bote_ranking_params* rp, int digest, int kernel, bote_sweep** out);
 /* Asynchronous on `hip_stream`: the sweep kernel, the exact fix-up of its
  * deferred near-tie configs, the (device-decided) overflow fallback and the
  * merge chain are all stream-ordered; no host synchronisation. */
@@ -388,6 +425,11 @@ int bote_sweep_split(const bote_sweep* s, uint64_t rank_begin, uint64_t rank_end
  * last launch (COV near-ties; more than 2^20 => the whole range was recomputed
  * on the generic path).  Synchronises `hip_stream`.  0 on the generic path. */
 int bote_sweep_deferred(bote_sweep* s, void* hip_stream, uint64_t* out);
+/* Configs of the last launch's range that meet every constraint (exact;
+ * deferred configs included, each config counted once whichever kernel decided
+ * it; the counts of disjoint ranges add).  On a sweep without constraints, the
+ * size of the launched range.  Synchronises `hip_stream`. */
+int bote_sweep_admitted(bote_sweep* s, void* hip_stream, uint64_t* out);
 /* Launch geometry chosen at creation (persistent grid, block size, LDS bytes). */
 int bote_sweep_grid(const bote_sweep* s, uint32_t* out_grid, uint32_t* out_block, uint32_t* out_lds_bytes);
 /* A sweep may be destroyed after its planet (it keeps the planet's device

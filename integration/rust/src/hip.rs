@@ -68,6 +68,14 @@ pub struct bote_objective {
     pub kind: u32,
     pub slot: u32,
 }
+/// a config is admitted iff the key an objective (kind, slot) would carry for it is <= max_key
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct bote_constraint {
+    pub kind: u32,
+    pub slot: u32,
+    pub max_key: u64,
+}
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
 pub struct bote_ranking_params {
@@ -201,6 +209,12 @@ extern "C" {
     pub fn bote_census_path(c: *const bote_census, out: *mut c_int) -> c_int;
     pub fn bote_census_last_kernel_ms(c: *mut bote_census, out_ms: *mut f32) -> c_int;
     pub fn bote_census_destroy(c: *mut bote_census) -> c_int;
+    pub fn bote_sweep_create_constrained(p: *const bote_planet, servers: *const u32, ns: u32, clients: *const u32,
+                                         nc: u32, n: u32, objs: *const bote_objective, n_obj: u32,
+                                         cons: *const bote_constraint, n_con: u32, k: u32,
+                                         rp: *const bote_ranking_params, digest: c_int, kernel: c_int,
+                                         out: *mut *mut bote_sweep) -> c_int;
+    pub fn bote_sweep_admitted(s: *mut bote_sweep, stream: *mut c_void, out: *mut u64) -> c_int;
 }
 
 /// Turns a status code into the panic the reference raises at the same place
